@@ -1,10 +1,24 @@
 #!/usr/bin/env python3
 """bench.py -- SMPL meshes/sec, forward + backward + Adam, batch 256 per GPU (BASELINE.json configs[2]).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus 1 --full         (the headline plus every extra measurement listed below)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
   python bench.py --mode infer            (BASELINE.json configs[1]: batch 64, J=17, eval forward + Tester epilogue)
+
+A PLAIN run does only what the headline needs: set up, W warm-up steps, the K timed steps, the outputs (--dump-outputs),
+one JSON line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the per-step spread, the workload).
+Everything else this script measures or checks - the power sample, the per-kernel rooflines, `arith_ab`, `also`, the
+multi-GPU collective timings, `parity_check` and `cpu_baseline` - runs only with `--full` (the --no-* options and
+--also then pick among them).
+
+--dump-outputs DIR writes what the timed path computed in its LAST timed step, as float32 DIR/<name>.npy (at most 44 MiB):
+train: loss, mesh (B, nv, 3: the model's vertices in the reference's vertex order), lift_pose (B, J, 3), and the parameters /
+gradients the step left in the optimizer's flat buffers as a fixed sample of 2^20 entries (params, grads; seeded, the same
+indices in every run); infer: mesh, joints (and pose3d on the captured / real-only paths).  An array over its share of the
+budget keeps a fixed, seeded sample of its leading-axis rows, in ascending order.  Inputs and initial weights are seeded:
+the same arguments give the same inputs in every run, so two builds can be compared output for output.
 
 ARITHMETIC OF THE HEADLINE (round 5).  The reference computes in fp32.  `value` is measured with the fp32 contractions emulated
 EXACTLY on the matrix pipe - every operand as three bf16 slices = 24-bit significands, six slice products per fp32 product
@@ -14,19 +28,20 @@ fp32), is the FAST MODE: measured in the same process at the same warm-up / step
 `value`.  `--arith f16x2|f32` or $P2M_GEMM_ARITH select another main arithmetic explicitly.
 
 Protocol: 20 warm-up + 50 timed steps by default; `value` / `ms_per_step` are wall-clock over the timed region,
-`ms_per_step_stats` the per-step median / p10 / p90 from one HIP event per step.  The default 1-GPU train run also reports, from
-the same process and after the timed region: `arith_ab` (f16x2 at full protocol, native-f32 MFMA briefly), `also` (configs[1]
-inference and configs[4] MANO B=512 train, each in the main arithmetic and in the fast mode; `--also none` to skip), and for N > 1
-`multi_gpu` (ranks seen over the job's backend, per-rank per-bucket all-reduce timings and the hidden fraction).  `python bench.py
---gpus N` with no launcher (WORLD_SIZE unset) starts its N ranks itself (round 6); either way NO line is printed unless N ranks,
-the nccl (RCCL) backend and N distinct GPUs are seen.
+`ms_per_step_stats` the per-step median / p10 / p90 from one HIP event per step.  With --full the default 1-GPU train run also
+reports, from the same process and after the timed region: `arith_ab` (f16x2 at full protocol, native-f32 MFMA briefly), `also`
+(configs[1] inference and configs[4] MANO B=512 train, each in the main arithmetic and in the fast mode; `--also none` to skip),
+and for N > 1 `multi_gpu` (ranks seen over the job's backend, per-rank per-bucket all-reduce timings and the hidden
+fraction).  `python bench.py --gpus N` with no launcher (WORLD_SIZE unset) starts its N ranks itself (round 6); either way NO
+line is printed unless N ranks, the nccl (RCCL) backend and N distinct GPUs are seen.
 
 One "step" (train mode) = one full reference train step (lib/core/base.py:122-148) on one synthetic batch that is
 already resident in HBM: FlatPose2Mesh forward (PoseNet + coarse-to-fine GCN, both on hand-written kernels), perm-reverse gather,
 joint regression, the five reference losses, backward, [gradient all-reduce], Adam.  Weak scaling: every rank owns `--batch`
 samples.  Rank 0 prints ONE JSON line.
 
-Extra objects on the line:
+Extra objects on the line (--full):
+  power            shader clock and package power sampled from a side thread during the timed steps
   roofline         the contraction family with the largest time in the step (bf16x3: the basis-inside-the-contraction tile
                    kernels): algorithmic fp32 FLOPs and algorithmic HBM bytes of its launches / their HIP-event time, against
                    the matrix-pipe peak expressed in algorithmic FLOPs (bf16x3: 2500 / 6 = 416.7 TFLOP/s; f16x2: 2500 / 3;
@@ -41,6 +56,7 @@ Extra objects on the line:
                    train step, timed on this host's cores (rank 0, N=1 only)
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -110,6 +126,9 @@ class TrainStep:
         # forward + backward = 3x the forward (dX and dW cost one forward each)
         self.dense_gflop_fwd = _dense_gflop_fwd(self.model.pose2mesh)
         self.dense_gflop_fwd_bwd = 3.0 * self.dense_gflop_fwd
+        # --dump-outputs: every step keeps a reference to its forward's outputs (no copy, no sync) for the dump after the
+        # timed steps
+        self.keep_outputs, self.outputs = False, None
 
     def loss_fn(self):
         """Forward + the five reference losses (fused form) -> the total loss: what train.GraphedTrainStep captures
@@ -124,6 +143,8 @@ class TrainStep:
             self.reducer.mark_step_start()          # (no-op unless the reducer's timing is switched on)
         self.opt.zero_grad()
         pred_mesh, lift_pose = m(self.pose2d)
+        if self.keep_outputs:
+            self.outputs = pred_mesh, lift_pose
         if not self.stock_losses:
             # base.py:130-143 (gather, J-regression, vertex/normal/edge/joint losses) in one fused HIP call
             mesh_total, _ = self.mesh_loss(pred_mesh, self.gt_mesh, self.gt_reg, self.one, self.one)
@@ -430,20 +451,22 @@ class PowerWatch:
 
 def timed_run(step, warmup, steps, barrier):
     """`warmup` untimed steps, then EXACTLY `steps` steps between two barrier + synchronize pairs -> (wall seconds,
-    per-step milliseconds).  The timed region is clean: no per-launch events in it, only one HIP event per STEP on the
-    main stream (recorded, never waited on inside the region) from which the per-step median / spread are read."""
+    per-step milliseconds, what the last step returned).  The timed region is clean: no per-launch events in it, only one
+    HIP event per STEP on the main stream (recorded, never waited on inside the region) from which the per-step median /
+    spread are read."""
     for _ in range(warmup):
         step()
     barrier()
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
+    out = None
     t0 = time.perf_counter()
     ev[0].record()
     for i in range(steps):
-        step()
+        out = step()
         ev[i + 1].record()
     barrier()
     dt = time.perf_counter() - t0
-    return dt, [ev[i].elapsed_time(ev[i + 1]) for i in range(steps)]
+    return dt, [ev[i].elapsed_time(ev[i + 1]) for i in range(steps)], out
 
 
 def step_stats(per_step_ms):
@@ -452,6 +475,45 @@ def step_stats(per_step_ms):
             "p10": round(float(np.percentile(a, 10)), 3), "p90": round(float(np.percentile(a, 90)), 3),
             "note": "per-step time between HIP events recorded on the main stream after every step of the timed region "
                     "(GPU-side; `value` and `ms_per_step` are wall-clock over the whole region, as the contract asks)"}
+
+
+DUMP_SEED = 20240607
+DUMP_FLAT_SAMPLE = 1 << 20                 # entries of the flat parameter / gradient buffers in the dump
+DUMP_CAP_BYTES = {"mesh": 32 << 20}        # per array (float32); any other array: 4 MiB -> <= 44 MiB in all
+
+
+def _sample_index(n, k, device):
+    """A fixed, seeded, ascending sample of k of the indices 0..n-1 (the same in every run and every build)."""
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+    return torch.from_numpy(idx).to(device)
+
+
+def step_outputs(step, last, infer):
+    """{name: device tensor}: what the timed path computed in its last step, as a caller of that path receives it.
+    `last` is what that step returned; `step` the TrainStep / InferStep behind it."""
+    if infer:
+        return dict(zip(("mesh", "joints", "pose3d"), last))
+    out = {"loss": last.detach().reshape(1)}
+    if step.outputs is not None:             # (the captured train step exposes its loss only)
+        pred_mesh, lift_pose = step.outputs
+        out["mesh"] = pred_mesh.detach()[:, step.perm, :]
+        out["lift_pose"] = lift_pose.detach()
+    idx = _sample_index(step.opt.numel, DUMP_FLAT_SAMPLE, step.opt.flat_param.device)
+    out["params"] = step.opt.flat_param[idx]
+    out["grads"] = step.opt.flat_grad[idx]
+    return out
+
+
+def dump_outputs(dirname, arrays):
+    """DIR/<name>.npy in float32 for every array; one over its cap keeps a fixed, seeded sample of its leading-axis rows."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().float()
+        cap = DUMP_CAP_BYTES.get(name, 4 << 20)
+        if t.numel() * 4 > cap:
+            rows = max(1, cap // (4 * (t.numel() // t.shape[0])))
+            t = t[_sample_index(t.shape[0], rows, t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy())
 
 
 DTYPE_NOTE = {
@@ -474,9 +536,9 @@ def main():
     ap.add_argument("--joint-set", default=None, choices=["coco", "human36", "mano"])
     ap.add_argument("--optimizer", default="adam", choices=["adam", "rmsprop"])
     ap.add_argument("--no-edge-loss", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=45.0)
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without parity_check and cpu_baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=45.0, help="--full: time budget of the cpu_baseline leg")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full without the per-kernel roofline passes")
     ap.add_argument("--stock-losses", action="store_true", help="use the stock-torch loss modules instead of p2m_mesh_loss")
     ap.add_argument("--train-graph", action="store_true",
                     help="train mode, 1 GPU: the whole step as one captured hipGraph (train.GraphedTrainStep)")
@@ -486,16 +548,24 @@ def main():
     ap.add_argument("--also", default=None,
                     help="comma list of extra legs measured after the main one and reported under `also` (1 GPU, default "
                          "train run only): infer = BASELINE configs[1] (batch 64, J=17, eval forward + Tester epilogue, "
-                         "captured hipGraph), mano = configs[4] (MANO-like, batch 512, train step).  Default: infer,mano; "
-                         "`none` switches them off")
+                         "captured hipGraph), mano = configs[4] (MANO-like, batch 512, train step).  Needs --full, whose "
+                         "default is infer,mano; `none` switches them off")
     ap.add_argument("--no-arith-ab", action="store_true",
-                    help="skip the same-process A/B of the other contraction arithmetics (`arith_ab`)")
+                    help="--full without the same-process A/B of the other contraction arithmetics (`arith_ab`)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every extra measurement and check after the timed steps: power sample, per-kernel "
+                         "rooflines, arith_ab, also, multi_gpu, parity_check, cpu_baseline (off: only the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step as DIR/<name>.npy (float32, "
+                         "<= 44 MiB in all)")
     ap.add_argument("--arith", default=None, choices=["bf16x3", "f16x2", "f32"],
                     help="contraction arithmetic of the MAIN measurement (`value`).  Default: $P2M_GEMM_ARITH if set, else "
                          "bf16x3 - the exact fp32 emulation (24-bit operands): the reference computes in fp32, so the headline "
                          "is quoted on an fp32-equivalent arithmetic; the package's fast mode f16x2 (22-bit operands, its "
                          "import-time default) is measured beside it under `arith_ab`, at the same protocol")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be >= 1")
     main_arith = args.arith or os.environ.get("P2M_GEMM_ARITH") or "bf16x3"
     if main_arith != ops.GEMM_ARITH:
         ops.GEMM_ARITH = main_arith
@@ -517,6 +587,10 @@ def main():
     for a in also:
         if a not in ("infer", "mano"):
             ap.error(f"--also: unknown leg {a!r} (infer, mano, none)")
+    if also and args.also and not args.full:
+        ap.error("--also measures extra legs: add --full")
+    if not args.full:
+        also = []
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` with no launcher around it: start the N ranks ourselves (one process per GPU, exactly
@@ -568,10 +642,19 @@ def main():
         step = p2m_train.GraphedTrainStep(eager_step.model, eager_step.opt, eager_step.loss_fn, warmup=2)
         args.warmup = max(args.warmup, 4)              # 2 eager steps, the capture, one replay before the clock starts
         graphed = True
-    with PowerWatch(local) as pwatch:
-        dt, per_step_ms = timed_run(step, args.warmup, args.steps, barrier)
+    keep = bool(args.dump_outputs) and not infer
+    if keep:
+        eager_step.keep_outputs = True
+    pwatch = PowerWatch(local) if args.full else None
+    with pwatch or contextlib.nullcontext():
+        dt, per_step_ms, last = timed_run(step, args.warmup, args.steps, barrier)
+    if args.dump_outputs and rank == 0:
+        # before anything else runs a step: the arrays of the LAST timed step
+        dump_outputs(args.dump_outputs, step_outputs(eager_step, last, infer))
+    if keep:
+        eager_step.keep_outputs, eager_step.outputs = False, None
     ksteps = min(args.steps, 10)          # steps of the per-kernel timing pass (untimed; ~1 200 HIP events per step)
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         # per-kernel rooflines: the SAME steps once more, launch by launch, every launch bracketed by HIP events on its
         # stream (a replayed graph cannot be bracketed node by node, so the graphed paths re-issue their launches eagerly)
         ops.TIMER = ops.KernelTimer()
@@ -587,7 +670,7 @@ def main():
                 step()
         torch.cuda.synchronize()
     timer_serial = None
-    if not args.no_kernel_timing and not infer and world == 1:
+    if args.full and not args.no_kernel_timing and not infer and world == 1:
         # ... and twice more with the weight-gradient launches on the MAIN stream (ops.DW_SIDE_STREAM off): in the step they
         # overlap the main stream's kernels, so their bracketed times above measure a shared GPU; here every launch has
         # the GPU to itself (`exclusive_serial` in the roofline objects)
@@ -608,7 +691,7 @@ def main():
 
     # ---- multi-GPU diagnostics (untimed, after the timed region): two more steps with HIP events around every collective
     multi = None
-    if world > 1 and not infer and eager_step.reducer is not None:
+    if args.full and world > 1 and not infer and eager_step.reducer is not None:
         red = eager_step.reducer
         red.timing = True
         for _ in range(2):
@@ -626,7 +709,7 @@ def main():
 
     # ---- same-process A/B of the contraction arithmetics (1 GPU, train): a fresh TrainStep per arithmetic, few steps
     arith_ab = None
-    if world == 1 and not infer and not args.no_arith_ab and not train_graph:
+    if args.full and world == 1 and not infer and not args.no_arith_ab and not train_graph:
         arith_ab = {}
         for ar in ("bf16x3", "f16x2", "f32"):
             if ar == main_arith:
@@ -638,7 +721,7 @@ def main():
             try:
                 st2 = TrainStep(device, args.batch, args.joint_set, world, edge_loss=not args.no_edge_loss,
                                 stock_losses=args.stock_losses, optimizer=args.optimizer)
-                d2, ps2 = timed_run(st2, w2, k2, barrier)
+                d2, ps2, _ = timed_run(st2, w2, k2, barrier)
                 stt = step_stats(ps2)
                 arith_ab[ar] = {"value": round(args.batch * k2 / d2, 2), "unit": "meshes/s", "steps": k2, "warmup": w2,
                                 "ms_per_step_median": stt["median"], "ms_per_step_p10_p90": [stt["p10"], stt["p90"]],
@@ -655,7 +738,7 @@ def main():
         def also_leg(leg):
             if leg == "infer":
                 st3 = InferStep(device, 64, "human36", path="graph")
-                d3, ps3 = timed_run(st3, 20, 100, barrier)
+                d3, ps3, _ = timed_run(st3, 20, 100, barrier)
                 return {"metric": "SMPL meshes/sec fwd at batch 64", "value": round(64 * 100 / d3, 2), "unit": "meshes/s",
                         "steps": 100, "warmup": 20, "ms_per_step": round(1000 * d3 / 100, 3),
                         "ms_per_step_stats": step_stats(ps3), "dtype": DTYPE_NOTE[ops.GEMM_ARITH],
@@ -663,7 +746,7 @@ def main():
                                     f"verts (padded {st3.V0}), FlatPose2Mesh eval forward + Tester epilogue, captured hipGraph of "
                                     f"the real-vertices-only inference path (python bench.py --mode infer)"}
             st3 = TrainStep(device, 512, "mano", 1, edge_loss=not args.no_edge_loss)
-            d3, ps3 = timed_run(st3, 5, 20, barrier)
+            d3, ps3, _ = timed_run(st3, 5, 20, barrier)
             return {"metric": "MANO meshes/sec fwd+bwd", "value": round(512 * 20 / d3, 2), "unit": "meshes/s",
                     "steps": 20, "warmup": 5, "ms_per_step": round(1000 * d3 / 20, 3),
                     "ms_per_step_stats": step_stats(ps3), "dtype": DTYPE_NOTE[ops.GEMM_ARITH],
@@ -727,7 +810,7 @@ def main():
                        **({"train_step": "one captured hipGraph (train.GraphedTrainStep); kernel timings from the same "
                                          "launches issued one by one after the timed region"} if train_graph else {})},
         }
-        pw = pwatch.report()
+        pw = pwatch.report() if pwatch is not None else None
         if pw is not None:
             line["power"] = pw
         # "MFMA util = meshes/s * FLOPs / 157.3e12" over the WHOLE step (all kernels, not only GEMM time)
@@ -898,9 +981,9 @@ def main():
             line["also"] = also_out
         if multi is not None:
             line["multi_gpu"] = multi
-        if world == 1 and not args.no_cpu_baseline and not infer:
+        if args.full and world == 1 and not args.no_cpu_baseline and not infer:
             line["parity_check"] = parity_check(step)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.joint_set, args.cpu_seconds, edge_loss=not args.no_edge_loss,
                                                 batch=64 if infer else 32, mode=args.mode)
         print(json.dumps(line), flush=True)

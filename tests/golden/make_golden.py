@@ -9,7 +9,10 @@ Fixtures (all deterministic: numpy PCG64 weights/inputs, fixed hull meshes):
   meshnet_<set>.npz  real lib/models/meshnet.Pose2Mesh: eval + train outputs, updated running stats,
                      gradient norms (+ a few full gradients) for a seeded upstream gradient
   flat_<set>.npz     real lib/models/pose2mesh_net.FlatPose2Mesh in eval(): cam_mesh, pose3d
-  chebconv.npz       real graph_conv_cheby (cheby_graph_conv.py:5-42) fwd/bwd at several shapes
+  chebconv.npz       real graph_conv_cheby (cheby_graph_conv.py:5-42) fwd/bwd at several shapes; case 0 here, the
+                     others in chebconv.part1.npz (one file would exceed 1 MiB; helpers.golden merges the parts)
+  live_mano.npz      real lib/models/meshnet.Pose2Mesh (MANO) in eval(): the output test_oracle_vs_live_reference_mano
+                     compares the oracle with (state seed 9, input seed 1, B = 3)
   loss_<set>.npz     real lib/core/loss.py classes driven exactly as lib/core/base.py:130-143 does: the five weighted
                      loss values and d(loss)/d(cam_mesh) (inputs are re-created from seeds by helpers.loss_case)
   state_<set>.npz    key / shape / checksum list of the real FlatPose2Mesh.state_dict() under torch.manual_seed(123)
@@ -142,7 +145,21 @@ def save_chebconv(gL_mano):
             out[f"c{ci}_dbeta"] = bn.bias.grad.numpy()
             out[f"c{ci}_rm"] = bn.running_mean.numpy()
             out[f"c{ci}_rv"] = bn.running_var.numpy()
-    np.savez_compressed(os.path.join(HERE, "chebconv.npz"), **out)
+    np.savez_compressed(os.path.join(HERE, "chebconv.npz"), **{k: v for k, v in out.items() if k.startswith("c0_")})
+    np.savez_compressed(os.path.join(HERE, "chebconv.part1.npz"), **{k: v for k, v in out.items() if not k.startswith("c0_")})
+
+
+def save_live_mano(gL):
+    ns = ref_loader.load("mano")
+    J = synth.JOINT_SETS["mano"][0]
+    net = ns.meshnet.get_model(5, 3, [L.copy() for L in gL])
+    net.load_state_dict(helpers.numpy_state(net.state_dict(), 9))
+    net.eval()
+    x = helpers.meshnet_input(3, J, seed=1)
+    with torch.no_grad(), ref_loader.cpu_cuda_shim():
+        y = net(x.clone())
+    np.savez_compressed(os.path.join(HERE, "live_mano.npz"), eval_out=y.numpy(), B=np.int64(3), J=np.int64(J))
+    ref_loader.load("human36")
 
 
 def real_regressor():
@@ -249,6 +266,9 @@ if __name__ == "__main__":
         _, gLh, _, revh, _, _ = ref_graphs("human36")
         save_demo(gLh, revh)
         sys.exit(0)
+    if sys.argv[1:] == ["live-mano"]:
+        save_live_mano(ref_graphs("mano")[1])
+        sys.exit(0)
     graphs = {}
     for js in ("mano", "human36", "coco"):
         graphs[js] = save_graphs(js)
@@ -259,6 +279,7 @@ if __name__ == "__main__":
     save_flat("mano", *graphs["mano"])
     save_flat("coco", *graphs["coco"])
     save_chebconv(graphs["mano"][0])
+    save_live_mano(graphs["mano"][0])
     for js in ("mano", "coco", "human36"):
         save_loss(js)
         print("loss", js)

@@ -127,8 +127,50 @@ def test_bench_line_helpers_and_cli():
     assert "3 exact bf16 slices" in b.DTYPE_NOTE["bf16x3"] and b.DTYPE_NOTE["f32"].startswith("f32 (native")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--also", "--no-arith-ab", "--mode", "--train-graph"):
+    for flag in ("--gpus", "--steps", "--warmup", "--also", "--no-arith-ab", "--mode", "--train-graph", "--full",
+                 "--dump-outputs"):
         assert flag in r.stdout, flag
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--also", "nonsense"], capture_output=True, text=True,
                        timeout=300)
     assert r.returncode != 0 and "unknown leg" in r.stderr
+    # the extra legs belong to --full; a plain run is the headline only
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--also", "infer"], capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode != 0 and "--full" in r.stderr
+
+
+def test_bench_dump_helpers(tmp_path):
+    """bench.py --dump-outputs (no GPU): float32 DIR/<name>.npy per output of the last step, the flat parameter / gradient
+    buffers as one fixed seeded sample (ascending, the same indices for both), an array over its cap cut to a fixed seeded
+    sample of its leading-axis rows, 64 MB at most in all."""
+    import importlib.util
+    import types
+
+    import torch
+    spec = importlib.util.spec_from_file_location("p2m_bench", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    n = 3_000_000
+    opt = types.SimpleNamespace(numel=n, flat_param=torch.arange(n, dtype=torch.float32),
+                                flat_grad=-torch.arange(n, dtype=torch.float32))
+    mesh = torch.randn(1024, 3000, 3)                         # 36.9 MB: over the mesh cap
+    step = types.SimpleNamespace(outputs=(mesh, torch.randn(1024, 17, 3, dtype=torch.float64)),
+                                 perm=torch.arange(2999, -1, -1), opt=opt)
+    arrays = b.step_outputs(step, torch.tensor(2.5, dtype=torch.float64, requires_grad=True) * 1, False)
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), arrays)
+    names = ["grads.npy", "lift_pose.npy", "loss.npy", "mesh.npy", "params.npy"]
+    assert sorted(os.listdir(tmp_path / "a")) == names
+    z = {f[:-4]: np.load(tmp_path / "a" / f) for f in names}
+    assert all(a.dtype == np.float32 for a in z.values())
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64e6
+    assert z["loss"].tolist() == [2.5] and z["lift_pose"].shape == (1024, 17, 3)
+    p, g = z["params"], z["grads"]
+    assert p.shape == (1 << 20,) and (np.diff(p) > 0).all() and (p == -g).all()
+    rows = z["mesh"]
+    assert rows.shape[1:] == (3000, 3) and 0 < rows.shape[0] < 1024 and rows.nbytes <= 32 << 20
+    full = mesh.flip(1).numpy()                                # the perm gather, reversed order
+    hit = [int(np.flatnonzero((full == r).all(axis=(1, 2)))[0]) for r in rows[:8]]
+    assert hit == sorted(hit)
+    for f in names:                                            # the same sample in every run
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))

@@ -373,7 +373,7 @@ def test_graph_replays_without_host_sync_keep_their_own_step_scalars(hip_libs):
 
 
 def test_bench_line_carries_the_contract_keys(hip_libs):
-    """`python bench.py` at a small batch, as the driver runs it for N = 1: ONE JSON line with the contract's keys, the
+    """`python bench.py --full` at a small batch: ONE JSON line with the contract's keys, the
     roofline object of the dominant kernel family (live HIP-event timing; PMC traffic with its code id and staleness flag), the
     untimed parity check against the CPU oracle, the CPU baseline object and - where the amdgpu hwmon files exist - the
     shader clock / package power sampled during the timed steps."""
@@ -382,8 +382,8 @@ def test_bench_line_carries_the_contract_keys(hip_libs):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "2", "--batch", "32", "--also", "none",
-                        "--no-arith-ab", "--cpu-seconds", "2"], cwd=root, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "2", "--batch", "32", "--also",
+                        "none", "--no-arith-ab", "--cpu-seconds", "2"], cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -406,3 +406,43 @@ def test_bench_line_carries_the_contract_keys(hip_libs):
         assert 100 <= pw["sclk_mhz_median"] <= 3000 and 50 <= pw["power_w_median"] <= 2000 and pw["samples"] >= 3
         if rf["bound"] == "mfma":
             assert abs(rf["frac_at_step_sclk"] - rf["frac"] * 2400 / pw["sclk_mhz_median"]) < 1e-3
+
+
+@pytest.mark.parametrize("mode", ["train", "infer"])
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(hip_libs, tmp_path, mode):
+    """`python bench.py` without --full: the headline keys and none of the --full objects, exactly --steps timed steps,
+    and with --dump-outputs the arrays of the last timed step as float32 .npy files (64 MB at most)."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+    from pose2mesh_release_amd import synth
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, "bench.py", "--mode", mode, "--steps", "4", "--warmup", "1", "--batch", "16",
+                        "--dump-outputs", str(out)], cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["unit"] == "meshes/s" and d["higher_is_better"] is True
+    assert d["dtype"] and d["ms_per_step"] > 0 and abs(d["value"] * d["ms_per_step"] - 16 * 1000) <= 1e-2 * 16 * 1000
+    for k in ("power", "roofline", "roofline_sparse", "kernel_ms_per_step", "arith_ab", "also", "multi_gpu", "parity_check",
+              "cpu_baseline"):
+        assert k not in d, k
+    js = "coco" if mode == "train" else "human36"
+    J = synth.JOINT_SETS[js][0]
+    want = {"mesh": (16, 6890, 3)}
+    if mode == "train":
+        want.update(loss=(1,), lift_pose=(16, J, 3), params=(1 << 20,), grads=(1 << 20,))
+    else:
+        want.update(joints=(16, J, 3), pose3d=(16, J, 3))
+    assert sorted(os.listdir(out)) == sorted(n + ".npy" for n in want)
+    assert sum(os.path.getsize(out / (n + ".npy")) for n in want) <= 64e6
+    for n, shape in want.items():
+        a = np.load(out / (n + ".npy"))
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all(), n
+    if mode == "train":
+        assert np.abs(np.load(out / "grads.npy")).max() > 0

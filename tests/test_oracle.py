@@ -10,8 +10,6 @@ import meshnet_oracle as mo
 import ref_loader
 from pose2mesh_release_amd import synth
 
-needs_ref = pytest.mark.skipif(not ref_loader.available(), reason="reference tree not mounted")
-
 
 def test_compute_perm_known_answer():
     """The reference's only golden vector (lib/coarsening.py:261-262)."""
@@ -109,9 +107,18 @@ def test_feature_axis_interpolation_closed_forms():
     assert (pm - torch.nn.functional.interpolate(x, size=128, mode="linear")).abs().max() < 1e-6
 
 
-@needs_ref
-@pytest.mark.reference
 def test_oracle_vs_live_reference_mano():
+    """The oracle against the real reference's MANO Pose2Mesh in eval(): against that model's output stored in
+    tests/golden/live_mano.npz (make_golden.py), and against the live reference itself where its tree is present."""
+    z = helpers.golden("live_mano.npz")
+    gL, _, _ = helpers.golden_graphs("mano")
+    J = synth.JOINT_SETS["mano"][0]
+    sd = helpers.numpy_state(mo.init_state(J, mo.trim_graph_list(gL), True), 9)
+    x = helpers.meshnet_input(3, J, seed=1)
+    out, _, _ = helpers.oracle_run(sd, helpers.oracle_graphs(gL), x, True, False)
+    assert helpers.max_vertex_l2(out, z["eval_out"]) < 2e-6
+    if not ref_loader.available():
+        return
     ns = ref_loader.load("mano")
     J, skel, flip, levels = synth.JOINT_SETS["mano"]
     _, faces = synth.hull_mesh(778, 0)

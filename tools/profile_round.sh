@@ -14,13 +14,17 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   tail -4 gpurun_out/${T}_gputests.log
   cp gpurun_out/parity_maxima.json gpurun_out/${T}_parity_maxima.json 2>/dev/null
 fi
-python bench.py > gpurun_out/${T}_bench.json 2> gpurun_out/${T}_bench.err
-python bench.py --mode infer > gpurun_out/${T}_bench_infer.json 2>> gpurun_out/${T}_bench.err
-python bench.py --joint-set mano --batch 512 --no-cpu-baseline --no-arith-ab > gpurun_out/${T}_bench_mano.json 2>> gpurun_out/${T}_bench.err
-python bench.py --optimizer rmsprop --no-cpu-baseline --no-arith-ab --steps 10 --warmup 5 > gpurun_out/${T}_bench_rmsprop.json 2>> gpurun_out/${T}_bench.err
-python bench.py --arith f16x2 --no-cpu-baseline --no-arith-ab --also none > gpurun_out/${T}_bench_f16x2.json 2>> gpurun_out/${T}_bench.err
+# the bench lines: --full for the rooflines, arith_ab, the other configurations, parity check and CPU baseline; they are
+# written to $OUT (default profile_out/ under the repo root)
+OUT=${OUT:-$R/profile_out}
+mkdir -p "$OUT"
+python bench.py --full > "$OUT/${T}_bench.json" 2> "$OUT/${T}_bench.err"
+python bench.py --full --mode infer > "$OUT/${T}_bench_infer.json" 2>> "$OUT/${T}_bench.err"
+python bench.py --full --joint-set mano --batch 512 --no-cpu-baseline --no-arith-ab > "$OUT/${T}_bench_mano.json" 2>> "$OUT/${T}_bench.err"
+python bench.py --full --optimizer rmsprop --no-cpu-baseline --no-arith-ab --steps 10 --warmup 5 > "$OUT/${T}_bench_rmsprop.json" 2>> "$OUT/${T}_bench.err"
+python bench.py --full --arith f16x2 --no-cpu-baseline --no-arith-ab --also none > "$OUT/${T}_bench_f16x2.json" 2>> "$OUT/${T}_bench.err"
 for f in bench bench_infer bench_mano bench_rmsprop bench_f16x2; do python -c "
-import json;j=json.load(open('gpurun_out/${T}_$f.json'));print('$f',j['value'],j['ms_per_step'],j.get('roofline',{}).get('frac'),j.get('roofline_sparse',{}).get('frac'),j.get('cpu_baseline',{}).get('value'))"; done
+import json;j=json.load(open('$OUT/${T}_$f.json'));print('$f',j['value'],j['ms_per_step'],j.get('roofline',{}).get('frac'),j.get('roofline_sparse',{}).get('frac'),j.get('cpu_baseline',{}).get('value'))"; done
 bash tools/rocprof_stats.sh ${T}_train --steps 6 --warmup 3 --no-kernel-timing --no-cpu-baseline --no-arith-ab --also none > /dev/null 2>&1
 bash tools/rocprof_stats.sh ${T}_infer --mode infer --steps 20 --warmup 5 --no-kernel-timing --no-cpu-baseline > /dev/null 2>&1
 bash tools/trace_step.sh ${T} > gpurun_out/${T}_trace.out 2>&1
