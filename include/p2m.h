@@ -467,6 +467,43 @@ int p2m_mesh_epilogue(const float* cam_mesh, int32_t V0, const int32_t* perm, in
                       const int32_t* jr_ptr, const int32_t* jr_idx, const float* jr_val, int32_t J,
                       float* mesh, float* joints, int32_t B, void* stream);
 
+/* ---- evaluation (lib/coord_utils.py:127-149, data/PW3D/dataset.py:273-286,322-375, data/Human36M/dataset.py:514-572) ----
+ * Batched similarity (Procrustes) alignment, rigid_transform_3D / rigid_align (coord_utils.py:127-149): for each of nb
+ * pairs of point sets A, B [N, 3] (N >= 1): cA, cB centroids, H = (A - cA)^T (B - cB) / N, R the proper rotation
+ * maximising tr(R H) (the reference's SVD with its det < 0 fix), c = (s1 + s2 +- s3) / varP (varP: population variance of
+ * A summed over the axes), t = cB - c R cA, and optionally A2 = c R A + t.  Out: c [nb], R [nb, 3, 3] (row-major,
+ * A2 = c R a + t), t [nb, 3], A2 [nb, N, 3] or NULL.  Centroids, H and varP are accumulated in fp64 and the 3x3 solve
+ * runs in fp64.  varP == 0 (all points of a set coincide): that set's c, t and A2 are non-finite, as in the reference.
+ * One wave per set for N <= 256, one block per set above.                                                            */
+int p2m_rigid_align(const float* A, const float* B, int32_t nb, int32_t N, float* c, float* R, float* t, float* A2,
+                    void* stream);
+/* The Tester's / dataset.evaluate()'s per-sample metrics of a batch, one block per sample, one launch:
+ *   stage A  JA = RA @ pred (CSR ra_*, JA <= 64 joints) or pred_joints_A [B, JA, 3]; the ground truth's joints are
+ *            gt_joints_A [B, JA, 3] or RA @ gt (given joints are used as given: compute_both_err's pred_joint and
+ *            reg_pose3d; ra_* may be NULL when both are given).  Both meshes and both joint sets are centred on their own joint
+ *            root_A.  mpjpe_A [B, nsub_A] = per-joint L2 over the subset sub_A (NULL: all JA joints, nsub_A ignored),
+ *            mpvpe [B] = mean per-vertex L2                              (dataset.py:273-286; PW3D 339-352, H36M 535-545)
+ *   stage E  (JE > 0) JE = RE @ (A-centred mesh); the ground truth is gt_joints_E [B, JE, 3] (the annotation's joint_cam,
+ *            used as given) or RE @ (A-centred gt), both re-centred on root_E and cut to sub_E.  mpjpe_E, pa_mpjpe_E
+ *            [B, nsub_E]: per-joint L2 before / after p2m_rigid_align's alignment of prediction onto ground truth
+ *                                                                        (PW3D 363-372, H36M 558-567)
+ *   pa_mesh  the A-centred prediction mesh aligned onto the A-centred ground truth mesh: pa_mpvpe [B] = mean per-vertex L2
+ *            (FreiHAND's PA-MPVPE; PW3D 360-361, commented out there)
+ * pred_mesh, gt_mesh [B, nv, 3] in mesh-model order; gt_mesh is read as gt_mesh * gt_mesh_scale (the Tester's x 1000,
+ * base.py:201).  Rows b >= B_real are padding: never read, their outputs written as 0.  Accumulation in fp64, fixed
+ * reduction orders, no atomics: bitwise reproducible; no allocation or synchronisation (capturable).
+ * sample_means [B, 5] (fp64, optional): the per-sample means of mpjpe_E, pa_mpjpe_E, mpjpe_A, mpvpe, pa_mpvpe.
+ * totals (fp64, optional; needs sample_means): [n_groups + 1][6] running sums, ADDED to by a one-block launch behind the
+ * evaluation in sample order: row 0 all samples, row 1 + g the samples with group[b] == g (group: [B] int32 or NULL;
+ * ids outside [0, n_groups) count in row 0 only); column 0 the sample count, 1..5 the sums of the five means.           */
+int p2m_mesh_eval(const float* pred_mesh, const float* gt_mesh, int32_t B, int32_t B_real, int32_t nv, float gt_mesh_scale,
+                  const int32_t* ra_ptr, const int32_t* ra_idx, const float* ra_val, int32_t JA, int32_t root_A,
+                  const int32_t* sub_A, int32_t nsub_A, const float* pred_joints_A, const float* gt_joints_A,
+                  const int32_t* re_ptr, const int32_t* re_idx, const float* re_val, int32_t JE, int32_t root_E, const int32_t* sub_E,
+                  int32_t nsub_E, const float* gt_joints_E, int32_t pa_mesh, float* mpjpe_A, float* mpvpe, float* mpjpe_E,
+                  float* pa_mpjpe_E, float* pa_mpvpe, double* sample_means, const int32_t* group, int32_t n_groups,
+                  double* totals, void* stream);
+
 /* ---- PoseNet, the 2D -> 3D lifter in front of MeshNet (lib/models/posenet.py:11-92) ---------------------------------
  * A 4096-wide residual MLP over B rows.  Every Linear (posenet.py:19,22,59,68: F.linear and its autograd) is a
  * weight-streaming contraction at these batch sizes and runs on p2m_gemm_tn, the reduction-split contraction with both

@@ -104,6 +104,9 @@ HIP_SYMBOLS = {
     "p2m_pn_stage_bwd": (_c.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp,
                                     _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
     "p2m_chebconv_fwd": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "p2m_rigid_align": (_c.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "p2m_mesh_eval": (_c.c_int, [_vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp,
+                                 _vp, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
 }
 
 HOST_SYMBOLS = {
