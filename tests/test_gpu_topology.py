@@ -7,7 +7,10 @@ every other test uses:
   * a UV sphere          two poles of degree 72: their merged rows (pole + ring + second ring) exceed the tile caps, so
                          the levels they sit on get NO tile plan (p2m_graph_plan_info == 0), no paired operator, and the
                          class plan is refused (Pose2Mesh._class_plan -> None): the row kernels and the fine-resolution
-                         backward run INSIDE the network.
+                         backward run INSIDE the network;
+  * a UV sphere          whose poles just FIT the caps (degree 59: merged row 2 * 59 + 1 = 119 <= 120 union rows): the finest
+                         level keeps all three tile plans, with rows of 119 / 120 entries beside rows of ~19 - the tile
+                         kernels run inside the network on the longest rows a plan can hold (tests/tile_plan_ref.py).
 Graphs are built by the package's own build_coarse_graphs (C++ HEM), which tests/test_graph_prep.py pins to the
 reference's lib/graph_utils.py:75-95 / lib/coarsening.py:214-258."""
 import numpy as np
@@ -42,6 +45,8 @@ def _graphs(kind):
         _, faces = synth.hull_mesh(6890, 3)
     elif kind == "hull7000":
         _, faces = synth.hull_mesh(7000, 0)
+    elif kind == "uv_sphere_poles_fit":
+        faces = _uv_sphere_faces(60, 59)                   # 3542 vertices, poles of degree 59
     else:
         faces = _uv_sphere_faces(60, 72)                   # 4322 vertices, poles of degree 72
     _, gL, _, _ = graph_utils.build_coarse_graphs(faces, J, skel, flip, levels=levels)
@@ -110,3 +115,16 @@ def test_high_degree_vertices_take_the_no_plan_paths_inside_the_network(hip_libs
         assert any(info["plans"][i][0] == 0 and info["plans"][i][2] == 0 for i in split_lv), str(info["plans"])
         assert not any(info["classes"]), str(info["classes"])
     _run("uv_sphere", 3, expect)
+
+
+def test_high_degree_vertices_that_fit_the_caps_take_the_tile_kernels(hip_libs):
+    import tile_plan_ref as tp
+    gL, _ = _graphs("uv_sphere_poles_fit")
+    want = tp.Plans(gL[0])                                  # the planner restated on the CPU: what the level should get
+    assert all(t > 0 for t in want.plan_tiles) and min(int(r.max()) for r in want.row_len) >= 100, want.describe()
+
+    def expect(info):
+        assert info["split"][0], info
+        # the finest level carries the poles (merged rows of 119 entries, 120 in the paired operator) and keeps every plan
+        assert info["plans"][0] == want.plan_tiles and all(t > 0 for t in info["plans"][0]), str(info["plans"])
+    _run("uv_sphere_poles_fit", 3, expect)
