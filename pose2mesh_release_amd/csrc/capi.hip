@@ -365,8 +365,8 @@ extern "C" int p2m_graph_create(const int32_t* row_ptr, const int32_t* col, cons
         if (rc2 == P2M_OK && g->plan[2].ntiles > 0) {
           g->n_pair_real = (int)preal.size();
           g->n_pair_fake = (int)pfake.size();
-          preal.resize(preal.size() + 64, 0);
-          pfake.resize(pfake.size() + 64, 0);
+          preal.resize(preal.size() + ID_SLACK, 0);
+          pfake.resize(pfake.size() + ID_SLACK, 0);
           if ((rc2 = upload(preal.data(), sizeof(int) * preal.size(), (void**)&g->pair_real_ids)) == P2M_OK)
             rc2 = upload(pfake.data(), sizeof(int) * pfake.size(), (void**)&g->pair_fake_ids);
         }
@@ -377,9 +377,10 @@ extern "C" int p2m_graph_create(const int32_t* row_ptr, const int32_t* col, cons
       return rc2;
     }
   }
-  // 64 zero entries of slack: the pipelined kernels prefetch ids a few 16-row stages ahead without bounds checks
-  real_ids.resize(real_ids.size() + 64, 0);
-  fake_ids.resize(fake_ids.size() + 64, 0);
+  // ID_SLACK zero entries of slack (p2m_common.h): the pipelined kernels prefetch ids a few 16-row stages ahead without
+  // bounds checks
+  real_ids.resize(real_ids.size() + ID_SLACK, 0);
+  fake_ids.resize(fake_ids.size() + ID_SLACK, 0);
   g->fake_a = fa;
   g->fake_b = fb;
   g->nnz = (int)mc.size();
@@ -525,9 +526,9 @@ extern "C" int p2m_graph_set_classes(p2m_graph_t gh, const int32_t* rep_of) {
   std::vector<float> tile_w(cdiv(n_rep > 0 ? n_rep : 1, 128), 0.f);
   for (int i = 0; i < n_rep; i++) tile_w[i / 128] += wts[i];
   const int n_pf = (int)pfake.size();
-  reps.resize(reps.size() + 64, 0);
-  wts.resize(wts.size() + 64, 0.f);
-  pfake.resize(pfake.size() + 64, 0);
+  reps.resize(reps.size() + ID_SLACK, 0);
+  wts.resize(wts.size() + ID_SLACK, 0.f);
+  pfake.resize(pfake.size() + ID_SLACK, 0);
   std::vector<int> rep_v(rep_of, rep_of + V);
   // upload everything into locals and commit to the handle only when all of it succeeded: on failure the handle is
   // exactly what it was ("no classes"), and a retry neither leaks nor sees half-set fields

@@ -986,7 +986,7 @@ __global__ __launch_bounds__(256) void k_gemm_tn(TnArgs g) {
 // Loads are unconditional (rows past the end are clamped and their values zeroed; columns past Ktot / N are clamped
 // and never stored), with two register stages of lead and an LDS-only barrier, as in k_gemm_planes_ws.  In ROWS mode
 // the vertex ids of a stage are fetched two phases before the data loads that depend on them (g.ids is zero-padded
-// by 64 entries at bake time, so those 16-byte id loads need no bounds).
+// by ID_SLACK entries at bake time, so those 16-byte id loads need no bounds).
 // ---------------------------------------------------------------------------------------------
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
@@ -1136,6 +1136,11 @@ __global__ __launch_bounds__(512, 2) void k_gemm_tn_ws(TnArgs g) {
   i32x4 id0 = {0, 0, 0, 0}, id1 = {0, 0, 0, 0};
   f32x4 dbs = {0.f, 0.f, 0.f, 0.f};
 
+  // No bounds: the tables end in ID_SLACK (p2m_common.h) zero entries.  The prologue fetches stages 0 .. 4 whatever nst is,
+  // so the highest index read is r_begin + 4 * RK + 3 * 4 + 3 = r_begin + 79 <= nset - 1 + 79 < nset + ID_SLACK (r_begin <
+  // nset in every chunk that gets here: nst > 0); the loops stay below that (stage nst + 1: r_begin + 16 nst + 31 <=
+  // nset + 46).  The matching load_stage is range-checked: ids past the end are never used as rows of the set.
+  static_assert(ID_SLACK >= 5 * RK && RK == ID_STAGE_ROWS, "the id prefetch of the prologue reads stages 0 .. 4");
   auto load_ids = [&](int kc, i32x4& id) {
     if (ROWS) id = *reinterpret_cast<const i32x4*>(idp + (long)kc * RK);
   };

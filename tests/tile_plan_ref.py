@@ -236,9 +236,13 @@ class Plans:
 
 # ---- graph families -----------------------------------------------------------------------------------------------------
 
-def band(V, seed, fake_frac=0.4):
-    """tests/test_gpu_ops.py:_band_graph (ring + chords 5 and 17 over the real vertices, all vertices renumbered)."""
-    nreal = max(8, int(V * (1 - fake_frac)))
+def band(V, seed, fake_frac=0.4, nreal=None):
+    """tests/test_gpu_ops.py:_band_graph (ring + chords 5 and 17 over the real vertices, all vertices renumbered).
+    nreal: the number of real vertices, exactly (instead of the share 1 - fake_frac of V); the other V - nreal are isolated.
+    The chords stay distinct from 35 real vertices up."""
+    if nreal is None:
+        nreal = max(8, int(V * (1 - fake_frac)))
+    assert 8 <= nreal <= V
     i = np.arange(nreal)
     A = _sym(np.concatenate([i, i, i]), np.concatenate([(i + 1) % nreal, (i + 5) % nreal, (i + 17) % nreal]), V)
     return permuted(laplacian(A, V), seed)
