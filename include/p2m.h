@@ -279,6 +279,7 @@ int p2m_lerp_bwd_add(const float* g, float* dst, int64_t M, int32_t F, int32_t F
  * keep their (B, V, F) layout, only the launches iterate over the subset.  BatchNorm statistics still cover ALL
  * rows (the reference includes fake vertices, cheby_graph_conv.py:39): p2m_bn_finalize_rows merges both launches. */
 int p2m_graph_split_info(p2m_graph_t g, int32_t counts[2] /* n_real, n_fake */, float coef[2] /* a, b */);
+/* in_shift 1 needs an even V, as in p2m_cheb_basis_fwd (refused otherwise) */
 int p2m_cheb_basis_fwd_real(p2m_graph_t g, const float* X, float* T1c, float* T2c, int32_t B, int32_t F,
                             int32_t in_shift, const float* act_scale /* or NULL */, const float* act_shift, void* stream);
 /* ---- paired operator: the backward of an un-pooled conv at the COARSE resolution ------------------------------

@@ -647,6 +647,8 @@ extern "C" int p2m_cheb_basis_fwd_real(p2m_graph_t gh, const float* X, float* T1
   P2M_CHECK_ARG(in_shift == 0 || in_shift == 1, "in_shift must be 0 or 1");
   P2M_CHECK_ARG((act_scale == nullptr) == (act_shift == nullptr), "act_scale / act_shift must both be given or both NULL");
   if (B <= 0) return P2M_OK;
+  // as p2m_cheb_basis_fwd: with an odd V the last vertex would read row V >> 1 of a coarse input that has V >> 1 rows
+  P2M_CHECK_ARG(in_shift == 0 || (reinterpret_cast<const Graph*>(gh)->V % 2 == 0), "virtual un-pool needs an even vertex count");
   return basis_fwd_launch(gh, X, T1c, T2c, B, F, in_shift, 1, stream, act_scale, act_shift);
 }
 
