@@ -564,6 +564,35 @@ int p2m_adam_step_dev(float* param, const float* grad, float* exp_avg, float* ex
 int p2m_rmsprop_step_dev(float* param, const float* grad, float* square_avg, int64_t n, const float* hp, float alpha,
                          float eps, void* stream);
 
+/* ---- body-model layer: batched SMPL / MANO forward (csrc/body.hip) ----------------------------------------------------
+ * The forward of smplpytorch's SMPL_Layer (smpl_layer.py:65-158) and manopth's ManoLayer (manolayer.py:109-273, use_pca =
+ * False, axis-angle root) for a batch, all in device memory: batch_rodrigues through the quaternion (with its + 1e-8),
+ * v_posed = template + shapedirs beta + posedirs (R_j - I)_{j >= 1}, rest joints, the kinematic chain over `parents`, dense
+ * linear blend skinning, then + trans or - centre joint, times scale.  fp32 FMA in fixed orders, no atomics: a sample's
+ * result does not depend on the batch it is in.  Three launches on `stream`; nothing allocates or synchronises.
+ *   pose [B, 3 J] axis-angle; pose_mean [3 J] added to every row (MANO: zeros for the root, then hands_mean) or NULL;
+ *   betas [B, nb] (betas_per_sample != 0) or one [nb] row for all samples; trans [B, 3], or NULL: then chain joint
+ *   center_joint (>= 0) is subtracted from vertices and joints.
+ *   v_template [3 V]; dirs [nb + 9 (J - 1)][3 V]: shapedirs then posedirs, coefficient-major; weights_t [J][V];
+ *   joint_template [J, 3] = J_regressor . template and joint_shapedirs [J, 3, nb] = J_regressor . shapedirs (folded on the
+ *   host); parents [J] with parents[j] < j for j >= 1 (the CALLER validates: the table is device memory).
+ *   joints [B, n_joints_out, 3]: chain joint j goes to slot joint_slot[j] (-1: dropped), vertex tip_vert[t] of the result
+ *   to slot tip_slot[t] (ManoLayer's finger tips; the caller validates the indices).
+ *   extra [B, n_extra, 3] = regressor @ verts for a CSR regressor (xr_ptr / xr_idx / xr_val, fp64 accumulation), n_extra = 0: none.
+ *   workspace: p2m_body_workspace(B, J, nb) bytes, 16-byte aligned.
+ * Limits: 1 <= J <= 64, nb + 9 (J - 1) <= 640, n_tips, n_extra <= 64, every buffer 4-byte aligned.
+ * p2m_body_sample_tile / p2m_body_vertex_tile: samples / vertices per block of the skinning kernel (tests walk their edges). */
+int32_t p2m_body_sample_tile(void);
+int32_t p2m_body_vertex_tile(void);
+int64_t p2m_body_workspace(int32_t B, int32_t J, int32_t nb);
+int p2m_body_forward(const float* pose, const float* pose_mean, const float* betas, int32_t betas_per_sample,
+                     const float* trans, int32_t center_joint, float scale, int32_t B, int32_t V, int32_t J, int32_t nb,
+                     const float* v_template, const float* dirs, const float* weights_t, const float* joint_template,
+                     const float* joint_shapedirs, const int32_t* parents, const int32_t* joint_slot, int32_t n_joints_out,
+                     const int32_t* tip_vert, const int32_t* tip_slot, int32_t n_tips, const int32_t* xr_ptr,
+                     const int32_t* xr_idx, const float* xr_val, int32_t n_extra, void* workspace, int64_t workspace_bytes,
+                     float* verts, float* joints, float* extra, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

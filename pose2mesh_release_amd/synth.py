@@ -62,3 +62,76 @@ def synthetic_regressor(J, nv, seed=5):
         w = rng.random(6).astype(np.float32)
         R[j, idx] = w / w.sum()
     return R
+
+
+MANO_PARENTS = (-1, 0, 1, 2, 0, 4, 5, 0, 7, 8, 0, 10, 11, 0, 13, 14)      # the tree manolayer.py:196-230 hard-codes
+MANO_TIPS_RIGHT = (745, 317, 444, 556, 673)                               # manolayer.py:253
+MANO_JOINT_ORDER = (0, 13, 14, 15, 16, 1, 2, 3, 17, 4, 5, 6, 18, 10, 11, 12, 19, 7, 8, 9, 20)   # manolayer.py:259
+BODY_KINDS = ("smpl", "chain", "star", "mano")
+
+
+def body_checksum(model):
+    """Float64 checksum of a body-model dict's arrays (position-weighted, so a permutation changes it)."""
+    s = 0.0
+    for k in ("v_template", "shapedirs", "posedirs", "J_regressor", "weights", "parents", "betas", "hands_mean"):
+        if model.get(k) is None:
+            continue
+        a = np.asarray(model[k], dtype=np.float64).reshape(-1)
+        s += float(np.abs(a).sum() + (a * ((np.arange(a.size) % 97) + 1.0)).sum() / 97.0)
+    return s
+
+
+def body_model(kind, num_vertex=None, seed=0):
+    """Seeded synthetic stand-in for a licensed body model (the .pkl files are absent, like the real faces): a dict of
+    the arrays BodyModel takes, fp32, plus "kind", "seed", "num_vertex" and "checksum" (body_checksum, float64).
+
+      kind  "smpl"   24 joints, 10 betas, 207 pose directions, a random parents[j] < j tree, metres
+            "chain"  the same with parents[j] = j - 1 (depth J - 1);  "star": all parents 0
+            "mano"   16 joints on MANO's own tree (ManoLayer hard-codes it), hands_mean, five tip vertices, the 21-joint
+                     order, outputs x 1000
+    Template points lie on a squashed sphere, directions are small Gaussians, J_regressor rows are 12-sparse and sum to
+    1, skinning weights are 4-sparse and sum to 1.  num_vertex defaults to 6890 / 778."""
+    if kind not in BODY_KINDS:
+        raise ValueError(f"kind: one of {BODY_KINDS}, got {kind!r}")
+    mano = kind == "mano"
+    J, nb = (16, 10) if mano else (24, 10)
+    V = int(num_vertex) if num_vertex is not None else (778 if mano else 6890)
+    if V < 1:
+        raise ValueError("num_vertex < 1")
+    rng = np.random.default_rng([seed, BODY_KINDS.index(kind), V])
+    size = 0.1 if mano else 1.0
+    p = rng.standard_normal((V, 3))
+    p /= np.linalg.norm(p, axis=1, keepdims=True)
+    v_template = p * np.array([0.3, 0.9, 0.2]) * size
+    shapedirs = rng.standard_normal((V, 3, nb)) * 0.01 * size
+    posedirs = rng.standard_normal((V, 3, 9 * (J - 1))) * 0.002 * size
+    J_regressor = np.zeros((J, V))
+    nr = min(12, V)
+    for j in range(J):
+        w = rng.random(nr) + 0.05
+        J_regressor[j, rng.choice(V, size=nr, replace=False)] = w / w.sum()
+    weights = np.zeros((V, J))
+    nw = min(4, J)
+    for v in range(V):
+        w = rng.random(nw) + 0.05
+        weights[v, rng.choice(J, size=nw, replace=False)] = w / w.sum()
+    if mano:
+        parents = list(MANO_PARENTS)
+    elif kind == "chain":
+        parents = [-1] + list(range(J - 1))
+    elif kind == "star":
+        parents = [-1] + [0] * (J - 1)
+    else:
+        parents = [-1] + [int(rng.integers(0, j)) for j in range(1, J)]
+    f32 = np.float32
+    m = {"kind": kind, "seed": int(seed), "num_vertex": V,
+         "v_template": v_template.astype(f32), "shapedirs": shapedirs.astype(f32), "posedirs": posedirs.astype(f32),
+         "J_regressor": J_regressor.astype(f32), "weights": weights.astype(f32), "parents": parents,
+         "betas": (rng.standard_normal(nb) * 0.1).astype(f32)}
+    if mano:
+        m["hands_mean"] = (rng.standard_normal(3 * (J - 1)) * 0.3).astype(f32)
+        m["tip_vertices"] = list(MANO_TIPS_RIGHT) if V > max(MANO_TIPS_RIGHT) else [min(V - 1, (i + 1) * V // 6) for i in range(5)]
+        m["joint_order"] = list(MANO_JOINT_ORDER)
+        m["scale"] = 1000.0
+    m["checksum"] = body_checksum(m)
+    return m
