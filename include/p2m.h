@@ -505,6 +505,53 @@ int p2m_mesh_eval(const float* pred_mesh, const float* gt_mesh, int32_t B, int32
                   float* pa_mpjpe_E, float* pa_mpvpe, double* sample_means, const int32_t* group, int32_t n_groups,
                   double* totals, void* stream);
 
+/* ---- F-scores: batched nearest-vertex distances (csrc/fscore.hip) ------------------------------------------------------
+ * FreiHAND's F@th.  The reference ships no F-score code (its numbers come from the challenge server), so this comment is
+ * the definition and tests/fscore_ref.py its float64 restatement.  Per sample, with P the prediction and G the ground
+ * truth (G read as gt_mesh * gt_mesh_scale), both [nv, 3] after the variant's transform:
+ *   d_pred[i] = min_j |P_i - G_j|,  d_gt[j] = min_i |G_j - P_i|      (Euclidean; the index correspondence is not used)
+ *   near_pred = #{i: d_pred[i] < th} / nv,  near_gt = #{j: d_gt[j] < th} / nv                      (strict comparison)
+ *   F = 2 near_pred near_gt / (near_pred + near_gt), 0 when the sum is 0
+ * Variants (variants: bit 0 centred, bit 1 aligned; at least one):
+ *   centred  each mesh minus its own centre point: row `root` of the CSR regressor r_* (J rows) applied to that mesh (fp64),
+ *            or pred_centre / gt_centre [B, 3] (used as given; both or neither), or nothing (all NULL)
+ *   aligned  the centred prediction similarity-aligned onto the centred ground truth over all vertices: exactly
+ *            p2m_mesh_eval's pa_mesh transform (fp64), the published FreiHAND numbers
+ * A prepare launch writes the sets fp32 and coordinate-major into the workspace, about one per-sample origin (the centred
+ * ground truth's centroid) subtracted in fp64 before the rounding; the search takes min (px-qx)^2 + (py-qy)^2 + (pz-qz)^2
+ * in fp32 over LDS tiles of targets and sqrtf at the end: with M the largest |coordinate| of a sample's staged sets and
+ * u = 2^-24, a distance is within (2 sqrt(3) M + 6 d) u of the exact one.  A third launch adds the per-block integer
+ * counts in a fixed order and computes near_* and F in fp64.  No float atomics, no allocation, no synchronisation
+ * (capturable); bitwise reproducible, and a sample's results do not depend on the batch around it.
+ *   thresholds   HOST array of 1..4 positive finite values (read before the launch, passed by value)
+ *   workspace    p2m_nn_workspace(B, nv, nv) bytes of device memory, 16-byte aligned
+ *   d_pred, d_gt, pa_d_pred, pa_d_gt   [B, nv] or NULL (a variant that is off is never written)
+ *   counts       [B][nvar][2][n_thresholds] int32 or NULL: direction 0 counts d_pred, 1 counts d_gt; nvar = variants
+ *                present, centred first
+ *   scores       [B][nvar][3][n_thresholds] fp64 or NULL: near_pred, near_gt, F
+ *   totals       (optional; needs scores) [n_groups + 1][1 + nvar * 3 * n_thresholds] fp64 running sums, ADDED to in sample
+ *                order: row 0 all samples, row 1 + g the samples with group[b] == g (ids outside [0, n_groups) count in row 0
+ *                only); column 0 the sample count, then the sums of the scores in their layout
+ * Rows b >= B_real are padding: never read, every output of theirs written as 0, not counted.
+ * p2m_point_nn: the bare two-way search between nb pairs of point sets A [nb, nA, 3], B [nb, nB, 3] (nA != nB allowed): dAB
+ * [nb, nA] = distance of each point of A to the nearest of B, dBA [nb, nB] the other way (one of them may be NULL).  No
+ * transform; the sets are still staged about a per-pair origin (the centroid of B).  Workspace: p2m_nn_workspace(nb, nA, nB).
+ * p2m_nn_target_tile: targets per LDS tile; p2m_nn_query_tile(n): queries per block for sets of at most n points (the
+ * search picks the queries per lane by the larger set of the call); tests walk the edges of both.
+ * Errors (P2M_ERR_INVALID, nothing launched): NULL required pointers, nv < 1, n_thresholds outside 1..4, a non-positive or
+ * non-finite threshold, B * nv * 3 >= 2^31, a workspace that is too small or misaligned.                                 */
+int32_t p2m_nn_target_tile(void);
+int32_t p2m_nn_query_tile(int32_t n);
+int64_t p2m_nn_workspace(int32_t B, int32_t nA, int32_t nB);
+int p2m_mesh_fscore(const float* pred_mesh, const float* gt_mesh, int32_t B, int32_t B_real, int32_t nv, float gt_mesh_scale,
+                    const int32_t* r_ptr, const int32_t* r_idx, const float* r_val, int32_t J, int32_t root,
+                    const float* pred_centre, const float* gt_centre, int32_t variants, const float* thresholds,
+                    int32_t n_thresholds, void* workspace, int64_t workspace_bytes, float* d_pred, float* d_gt,
+                    float* pa_d_pred, float* pa_d_gt, int32_t* counts, double* scores, const int32_t* group, int32_t n_groups,
+                    double* totals, void* stream);
+int p2m_point_nn(const float* A, const float* B, int32_t nb, int32_t nA, int32_t nB, float* dAB, float* dBA, void* workspace,
+                 int64_t workspace_bytes, void* stream);
+
 /* ---- PoseNet, the 2D -> 3D lifter in front of MeshNet (lib/models/posenet.py:11-92) ---------------------------------
  * A 4096-wide residual MLP over B rows.  Every Linear (posenet.py:19,22,59,68: F.linear and its autograd) is a
  * weight-streaming contraction at these batch sizes and runs on p2m_gemm_tn, the reduction-split contraction with both

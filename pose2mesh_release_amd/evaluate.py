@@ -8,6 +8,15 @@ data/Human36M/dataset.py:514-572, lib/coord_utils.py:127-149).
   MeshEvaluator                                 per-sample metrics of a batch in one launch (p2m_mesh_eval) and running
                                                 fp64 totals on the device; summary() syncs once.
   compute_both_err                              drop-in for the datasets' compute_both_err (two floats per batch).
+  FScoreEvaluator                               FreiHAND's F@5 mm / F@15 mm per sample (p2m_mesh_fscore): nearest-vertex
+                                                distances both ways between prediction and ground truth, centred and / or
+                                                similarity-aligned (PA-MPVPE's alignment), thresholded counts, F, running
+                                                fp64 totals; summary() syncs once.  The reference ships no F-score code:
+                                                the definition is the one in include/p2m.h, restated in float64 in
+                                                tests/fscore_ref.py.
+  nearest_distances(A, B)                       the bare two-way nearest-point search between [N, 3] / [nb, N, 3] and
+                                                [M, 3] / [nb, M, 3] CUDA tensors (p2m_point_nn): chamfer distances,
+                                                per-vertex error heat maps.
 
 Everything is accumulated in fp64 on the device, in fixed orders (bitwise reproducible), and the launches allocate and
 synchronise nothing, so an evaluator call can sit in a captured graph.  There is no CPU fallback: CPU tensors raise.
@@ -272,3 +281,186 @@ def compute_both_err(pred_mesh, target_mesh, pred_joint, target_joint, eval_join
     ev.reset()
     m = out["sample_means"][:, 2:4].mean(dim=0).cpu()
     return float(m[0]), float(m[1])
+
+
+def _workspace(nb, nA, nB, dev):
+    n = int(_lib.hip().p2m_nn_workspace(nb, nA, nB))
+    if n < 0:
+        raise ValueError(f"bad point-set shape ({nb}, {nA}, {nB})")
+    return torch.empty(max(n, 16), device=dev, dtype=torch.uint8), n
+
+
+def nearest_distances(A, B):
+    """(d_ab, d_ba): d_ab[..., i] = min_j |A_i - B_j| and d_ba[..., j] = min_i |B_j - A_i| for A [N, 3] or [nb, N, 3] and B
+    [M, 3] or [nb, M, 3] CUDA tensors (N != M allowed), fp32.  The points are staged about each pair's centroid of B (fp64
+    subtraction before the fp32 rounding), so the error scales with the sets' extent, not their position: at most
+    (2 sqrt(3) max|coordinate - centroid| + 6 d) 2^-24 per distance."""
+    if not (isinstance(A, torch.Tensor) and isinstance(B, torch.Tensor)) or A.dim() != B.dim() or A.dim() not in (2, 3) or \
+            A.shape[-1] != 3 or B.shape[-1] != 3 or A.shape[-2] < 1 or B.shape[-2] < 1 or \
+            (A.dim() == 3 and A.shape[0] != B.shape[0]):
+        raise ValueError(f"A, B: expected [N, 3] and [M, 3] or [nb, N, 3] and [nb, M, 3] tensors, got "
+                         f"{tuple(getattr(A, 'shape', ()))}, {tuple(getattr(B, 'shape', ()))}")
+    A, B = _cuda_f32(A, "A"), _cuda_f32(B, "B")
+    single = A.dim() == 2
+    nb = 1 if single else int(A.shape[0])
+    nA, nB = int(A.shape[-2]), int(B.shape[-2])
+    dev = A.device
+    d_ab = torch.empty((nb, nA), device=dev, dtype=torch.float32)
+    d_ba = torch.empty((nb, nB), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        ws, n = _workspace(nb, nA, nB, dev)
+        _lib.check(_lib.hip().p2m_point_nn(_p(A), _p(B), nb, nA, nB, _p(d_ab), _p(d_ba), _p(ws), n, _stream()),
+                   "p2m_point_nn")
+    return (d_ab[0], d_ba[0]) if single else (d_ab, d_ba)
+
+
+class FScoreEvaluator:
+    """fs = FScoreEvaluator(nv, regressor=None, root=0, thresholds=(5.0, 15.0), centred=True, aligned=True,
+                            gt_mesh_scale=1.0, n_groups=32)
+    out = fs(pred_mesh, gt_mesh, pred_root=None, gt_root=None, B_real=None, group=None)
+    totals = fs.summary();  fs.reset()
+
+    Per sample (include/p2m.h, p2m_mesh_fscore, has the definition): d_pred[i] = distance of prediction vertex i to the
+    NEAREST ground-truth vertex, d_gt[j] the other way; near_pred / near_gt = the share of them strictly below a threshold;
+    F = their harmonic mean (0 when both are 0).
+      centred  both meshes minus their own centre point: row `root` of `regressor` ([J, nv] dense) applied to each mesh, or
+               pred_root / gt_root [B, 3] given per call (used as they are; both or neither), or - without a regressor and
+               without roots - nothing: the meshes are compared where they are
+      aligned  the centred prediction similarity-aligned onto the centred ground truth over all vertices (MeshEvaluator's
+               pa_mesh transform): the published FreiHAND F-scores
+    pred_mesh / gt_mesh: [B, nv, 3] CUDA tensors; gt_mesh is read times gt_mesh_scale; thresholds (1..4) are in the unit of
+    the prediction.  B_real, group: as MeshEvaluator's.
+
+    A call launches on the current stream and returns per-sample device tensors: f, near_pred, near_gt [B, T] (fp64) and
+    d_pred, d_gt [B, nv] (fp32) for the centred variant, the same with a pa_ prefix for the aligned one, and counts
+    [B, variants, 2, T] (int32).  They are buffers reused per batch size, overwritten by the next call of the same size, and
+    the call adds the batch to running fp64 totals on the device: no allocation after the first call of a size and no sync,
+    so a call can sit in a single-stream captured graph."""
+
+    def __init__(self, nv, regressor=None, root=0, thresholds=(5.0, 15.0), centred=True, aligned=True, gt_mesh_scale=1.0,
+                 n_groups=32):
+        self.nv, self.root, self.n_groups = int(nv), int(root), int(n_groups)
+        self.centred, self.aligned, self.gt_mesh_scale = bool(centred), bool(aligned), float(gt_mesh_scale)
+        if self.nv < 1:
+            raise ValueError("nv < 1")
+        if not (self.centred or self.aligned):
+            raise ValueError("at least one of centred, aligned")
+        th = [float(t) for t in _np.asarray(thresholds, dtype=_np.float64).reshape(-1)]
+        if not 1 <= len(th) <= 4 or not all(_np.isfinite(t) and t > 0 for t in th):
+            raise ValueError(f"thresholds: 1..4 positive finite values expected, got {thresholds}")
+        self.thresholds = tuple(th)
+        self._th = (_ct.c_float * len(th))(*th)
+        self._host = {}
+        if regressor is not None:
+            r = _np.asarray(regressor, dtype=_np.float32)
+            if r.ndim != 2 or r.shape[1] != self.nv or not 0 <= self.root < r.shape[0]:
+                raise ValueError(f"regressor: expected [J > root, {self.nv}], got {r.shape}")
+            t = _loss._regressor_tables(r[self.root:self.root + 1], self.nv)       # only the centre's row is read
+            self._host.update(r_ptr=t["jr_ptr"], r_idx=t["jr_idx"], r_val=t["jr_val"])
+        self.variants = (1 if self.centred else 0) | (2 if self.aligned else 0)
+        self._prefixes = ([""] if self.centred else []) + (["pa_"] if self.aligned else [])
+        self._dev = None
+        self._bufs = {}
+        self.totals = None
+
+    @property
+    def _ncol(self):
+        return 1 + len(self._prefixes) * 3 * len(self.thresholds)
+
+    def _device_tables(self, dev):
+        if self._dev is None or self._dev[0] != dev:
+            d = {k: torch.from_numpy(_np.ascontiguousarray(v)).to(dev) for k, v in self._host.items()}
+            self._dev = (dev, d)
+            self.totals = torch.zeros((self.n_groups + 1, self._ncol), device=dev, dtype=torch.float64)
+            self._bufs = {}
+        return self._dev[1]
+
+    def reset(self):
+        """Clears the running totals (a device-side fill on the current stream)."""
+        if self.totals is not None:
+            self.totals.zero_()
+
+    def _buffers(self, B, dev):
+        b = self._bufs.get(B)
+        if b is None:
+            nvar, T = len(self._prefixes), len(self.thresholds)
+            b = {"counts": torch.zeros((B, nvar, 2, T), device=dev, dtype=torch.int32),
+                 "scores": torch.zeros((B, nvar, 3, T), device=dev, dtype=torch.float64),
+                 "group": torch.full((B,), -1, device=dev, dtype=torch.int32)}
+            for pre in self._prefixes:
+                b[pre + "d_pred"] = torch.zeros((B, self.nv), device=dev, dtype=torch.float32)
+                b[pre + "d_gt"] = torch.zeros((B, self.nv), device=dev, dtype=torch.float32)
+            b["ws"], b["ws_bytes"] = _workspace(B, self.nv, self.nv, dev)
+            self._bufs[B] = b
+        return b
+
+    @torch.no_grad()
+    def __call__(self, pred_mesh, gt_mesh, pred_root=None, gt_root=None, B_real=None, group=None):
+        for x in (pred_mesh, gt_mesh):
+            if not isinstance(x, torch.Tensor) or x.dim() != 3 or tuple(x.shape[1:]) != (self.nv, 3) or \
+                    x.shape != pred_mesh.shape:
+                raise ValueError(f"pred_mesh / gt_mesh: expected equal [B, {self.nv}, 3] tensors, got "
+                                 f"{tuple(getattr(x, 'shape', ()))}")
+        B = int(pred_mesh.shape[0])
+        B_real = B if B_real is None else int(B_real)
+        if not 0 <= B_real <= B:
+            raise ValueError(f"B_real = {B_real} outside [0, {B}]")
+        if (pred_root is None) != (gt_root is None):
+            raise ValueError("pred_root and gt_root: both or neither")
+        if pred_root is not None:
+            for x, n in ((pred_root, "pred_root"), (gt_root, "gt_root")):
+                if not isinstance(x, torch.Tensor) or tuple(x.shape) != (B, 3):
+                    raise ValueError(f"{n}: expected a [{B}, 3] tensor, got {tuple(getattr(x, 'shape', ()))}")
+        pred, gt = _cuda_f32(pred_mesh, "pred_mesh"), _cuda_f32(gt_mesh, "gt_mesh")
+        pr = gr = None
+        if pred_root is not None:
+            pr, gr = _cuda_f32(pred_root, "pred_root"), _cuda_f32(gt_root, "gt_root")
+        dev = pred.device
+        t = self._device_tables(dev)
+        buf = self._buffers(B, dev)
+        grp = None
+        if group is not None:
+            grp = buf["group"]
+            if isinstance(group, torch.Tensor) and group.is_cuda:
+                g = group.reshape(-1)[:B].to(torch.int32)
+            else:
+                g = torch.as_tensor(_np.asarray(group, dtype=_np.int32).reshape(-1)[:B]).to(dev, non_blocking=True)
+            if g.numel() < B_real:
+                raise ValueError(f"group: need >= {B_real} ids, got {g.numel()}")
+            grp[:g.numel()].copy_(g)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.hip().p2m_mesh_fscore(
+                _p(pred), _p(gt), B, B_real, self.nv, self.gt_mesh_scale, _p(t.get("r_ptr")), _p(t.get("r_idx")),
+                _p(t.get("r_val")), 1, 0, _p(pr), _p(gr), self.variants, self._th, len(self.thresholds), _p(buf["ws"]),
+                buf["ws_bytes"], _p(buf.get("d_pred")), _p(buf.get("d_gt")), _p(buf.get("pa_d_pred")), _p(buf.get("pa_d_gt")),
+                _p(buf["counts"]), _p(buf["scores"]), _p(grp), self.n_groups, _p(self.totals), _stream()), "p2m_mesh_fscore")
+        out = {"counts": buf["counts"]}
+        for v, pre in enumerate(self._prefixes):
+            out[pre + "near_pred"], out[pre + "near_gt"], out[pre + "f"] = (buf["scores"][:, v, k] for k in range(3))
+            out[pre + "d_pred"], out[pre + "d_gt"] = buf[pre + "d_pred"], buf[pre + "d_gt"]
+        return out
+
+    def _columns(self):
+        """Names of totals[:, 1:], in the layout of the scores: [variant][near_pred, near_gt, f][threshold]."""
+        return [f"{pre}{k}@{th:g}" for pre in self._prefixes for k in ("near_pred", "near_gt", "f") for th in self.thresholds]
+
+    def summary(self):
+        """Syncs once.  {"samples": n, "f@5": dataset mean of the per-sample F, "near_pred@5", "near_gt@5", ..., "pa_f@5",
+        ..., "groups": {g: {"samples": n_g, ...}}} over every sample since the last reset() (thresholds formatted with :g).
+        "groups" lists the groups that received samples."""
+        if self.totals is None:
+            return {"samples": 0}
+        tot = self.totals.cpu().numpy()
+        cols = self._columns()
+
+        def row(r):
+            n = tot[r, 0]
+            d = {"samples": int(n)}
+            for i, k in enumerate(cols):
+                d[k] = float(tot[r, 1 + i] / n) if n > 0 else float("nan")
+            return d
+        out = row(0)
+        groups = {g: row(g + 1) for g in range(self.n_groups) if tot[g + 1, 0] > 0}
+        if groups:
+            out["groups"] = groups
+        return out
