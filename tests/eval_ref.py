@@ -98,3 +98,29 @@ def summary(per_sample, group=None):
             out["groups"][int(g)] = {k: float(np.mean(v[m])) for k, v in per_sample.items()}
             out["groups"][int(g)]["samples"] = int(m.sum())
     return out
+
+
+def alignment_spectrum(A, B):
+    """How well one pair of sets [N, 3] fixes its rotation: dict of s (the singular values s1 >= s2 >= s3 of
+    H = (A - cA)^T (B - cB) / N), sign (of det H, +1 for det H = 0), gap = 2 (s2 + sign s3) / s1 (the distance between the
+    two largest eigenvalues of Horn's 4x4 matrix over s1; nan for H = 0 and for non-finite data) and varP (population
+    variance of A summed over the axes).  gap = 0: a one-parameter family of rotations attains the optimum."""
+    A, B = np.asarray(A, np.float64), np.asarray(B, np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        H = (A - A.mean(axis=0)).T @ (B - B.mean(axis=0)) / A.shape[0]
+        varP = float(np.var(A, axis=0).sum())
+    if not np.isfinite(H).all():
+        return {"s": np.full(3, np.nan), "sign": 1.0, "gap": float("nan"), "varP": varP}
+    s = np.linalg.svd(H, compute_uv=False)
+    sign = -1.0 if np.linalg.det(H) < 0 else 1.0
+    gap = float(2.0 * (s[1] + sign * s[2]) / s[0]) if s[0] > 0 else float("nan")
+    return {"s": s, "sign": sign, "gap": gap, "varP": varP}
+
+
+def optimum(A, B):
+    """(c, rms) of one pair: the optimal scale and the root-mean-square residual |c R A + t - B| over the points.  Both are
+    unique even where R is not (every maximiser of tr(R H) has the same c and the same residual); the residual is
+    evaluated at the SVD's maximiser, not from the closed form varB - lam^2 / varP, which cancels for exact similarities."""
+    c, R, t = rigid_transform_3D(A, B)
+    A2 = (c * R @ np.asarray(A, np.float64).T).T + t
+    return float(c), float(np.sqrt(np.mean(np.sum((A2 - np.asarray(B, np.float64)) ** 2, axis=-1))))
