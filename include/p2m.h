@@ -640,6 +640,120 @@ int p2m_body_forward(const float* pose, const float* pose_mean, const float* bet
                      const int32_t* xr_idx, const float* xr_val, int32_t n_extra, void* workspace, int64_t workspace_bytes,
                      float* verts, float* joints, float* extra, void* stream);
 
+/* ---- training-sample noise: synthetic 2D detector errors (csrc/sample.hip, csrc/p2m_philox.h) ---------------------------
+ * Every released recipe of the reference trains on noisy 2D input (use_gt_input: False): the dataset replaces the clean
+ * projected joints by synthetic detector errors on a dataloader worker (data/AMASS/dataset.py:311-330 and its siblings).
+ * These two entry points draw that noise on the device.  No allocation, no host synchronisation (capturable).
+ *
+ * Random numbers: ONE counter-based stream, Philox4x32-10 (multipliers D2511F53 / CD9E8D57, Weyl constants 9E3779B9 /
+ * BB67AE85).  key = the 64-bit seed; counter words 0, 1 = the 64-bit GLOBAL sample index first_index + b, word 2 =
+ * joint | stage << 8, word 3 = the draw-block index.  So a sample's result depends on (seed, its global index) alone, never
+ * on the batch it sits in.  state: two uint64 words in DEVICE memory {seed, first_index} - a captured graph replays with
+ * fresh numbers once the caller has advanced state[1] by B with an ordinary (captured) tensor add.
+ * A uniform is (word >> 8) * 2^-24: exact in fp32 and fp64.  A candidate point is (angle, radius) = two uniforms; one draw
+ * block holds two candidates: candidate c of a stage is block c >> 1, words 0, 1 (angle, radius) for even c, words 2, 3 for
+ * odd c.  Normals are Box-Muller on (1 - u0, u1): sqrt(-2 ln(1 - u0)) (cos, sin)(2 pi u1).  Stages:
+ *   0 jitter      500 candidates, radius in [ks_85, ks_50] around the joint itself
+ *   1 miss count, source 0 (the joint itself)   2000 candidates, radius in [ks_50, ks_10]
+ *   2 miss count, source 1 (the partner)        2000 candidates, likewise
+ *   3 miss point, source 0     4 miss point, source 1    up to 2000 candidates each, likewise
+ *   5 inversion   500 candidates, radius in [0, ks_50] around the partner
+ *   6 good        125 candidates, radius in [0, ks_85] around the joint itself
+ *   7 select      block 0: word 0 the miss-source uniform, word 1 the category uniform
+ *   8 table       block 0: word 0 the Bernoulli uniform, words 1, 2 the Box-Muller pair (u0, u1)
+ *   9 augment     joint 0, block 0: word 0 flip, words 1, 2 the rotation's Box-Muller pair, word 3 rot = 0 (p2m_train_sample)
+ * with ks_q = sqrt(area) 2 sigma_j sqrt(-2 ln q) (get_dist_wrt_ks, lib/noise_utils.py:18-24; a negative or NaN area counts
+ * as 0).  tests/sample_ref.py mirrors all of this in numpy, float64.
+ *
+ * p2m_pose_noise_coco: the distribution of synthesize_pose(joints, area, num_overlap = 0) (lib/noise_utils.py:17-285).
+ *   joints [B, 17, 3] (x, y, valid), area [B], sigmas [17] (the COCO OKS sigmas / 10), out [B, 17, 3] (x, y, 1 - or all 0 when
+ *   no error type was available), kind [B, 17] int8 or NULL: 0 jitter, 1 miss, 2 inversion, 4 good, -1 joint zeroed.
+ *   EVERY joint is synthesised, valid or not (the reference loops over all 17); validity enters through num_valid_joint
+ *   (the probability tables :70-83, :105-125, :161-166) and through the partner.  Facts of the reference that are kept:
+ *   near_joints has no valid entry and swap_exist is False (:14, :189, :231), so a joint's candidate sources are its own
+ *   position and, when its left / right partner's ORIGINAL validity is > 0, the partner's CURRENT coordinates: the loop
+ *   updates synth_joints in place, so the higher joint of a pair (2, 4, .., 16) sees the already synthesised lower one, (0, 0)
+ *   if that was zeroed.  Nine independent units per sample - the nose and eight pairs of two sequential steps -, one wave each.
+ *   Sampling scheme - EQUAL IN DISTRIBUTION to the reference, but restated, and defined here:
+ *     jitter / inversion / good   the reference draws N iid candidates and picks uniformly among those passing the distance
+ *                  mask (distance to the other source > r).  That has the distribution of the FIRST passing candidate of
+ *                  the sequence, and the type is unavailable if none of the N passes.  64 lanes evaluate 128 candidates a
+ *                  step and the first ballot hit ends the stage.  Without a second source candidate 0 is taken.
+ *     miss         n_s = passing candidates among 2000 of source s (mask: distance to the OTHER source > ks_50).  The pool
+ *                  of :143-151 is n_0 points of source 0 plus n_1 / 4 (integer) of source 1: the source is chosen by
+ *                  (word >> 8) (n_0 + n_1 / 4) < n_0 2^24 (exact integers), the point is the first passing candidate of
+ *                  that source's SEPARATE point stage, so it does not depend on the counts; unavailable when the pool is
+ *                  empty (or when none of the point stage's 2000 candidates passes).  Sources further apart than
+ *                  (ks_10 + ks_50) (1 + 2^-10) cannot fail each other's mask: then n_0 = n_1 = 2000 without counting.
+ *     category     availability zeroing and renormalisation of :256-276, then the category uniform times the sum of the
+ *                  available weights against their running sums in the order [jitter, miss, inversion, good] (swap = 0).
+ *   fp32; angles through sincospif(2 u) (accurate, not the fast intrinsics: the robustness band of tests/sample_ref.py is
+ *   derived from this operation sequence).  out must not overlap joints.
+ *
+ * p2m_pose_noise_table: generate_syn_error and its use (data/AMASS/dataset.py:77-89, 327-329) for any joint set:
+ *   out[b, j, :] = pose[b, j, :] + [weight_j > u] (mean_j + std_j n) / 256 * (W, H),  n two normals per (sample, joint).
+ *   pose, out [B, J, 2] (out may alias pose); mean, std [J, 2]; weight [J]; 1 <= J <= 32.  The reference's own table
+ *   (lib/noise_stats.py) is not part of this project: callers load it from their checkout.
+ * Errors (P2M_ERR_INVALID, nothing launched): NULL state or another required pointer, B < 1, J outside [1, 32], misaligned
+ * buffers (state: 8 bytes), aliasing as above.                                                                            */
+int p2m_pose_noise_coco(const float* joints, const float* area, const float* sigmas, const uint64_t* state, float* out,
+                        int8_t* kind, int32_t B, void* stream);
+int p2m_pose_noise_table(const float* pose, const float* mean, const float* std, const float* weight, int32_t J, float W,
+                         float H, const uint64_t* state, float* out, int32_t B, void* stream);
+
+/* ---- training samples: the whole chain mesh + camera -> the tensors of lib/core/base.py:124-126 (csrc/sample.hip) --------
+ * What the reference's datasets do per sample in numpy on dataloader workers (data/AMASS/dataset.py:246-330; Human36M,
+ * MuCo, COCO and SURREAL differ in where the joints come from), for a batch, in three launches (two without noise) on
+ * `stream`; nothing allocates or synchronises.  Steps, per sample b (global index state[1] + b):
+ *   joints     mesh_mm = (verts + trans) * mesh_scale in fp32 (trans NULL: 0; AMASS :205-211), joint = regressor row .
+ *              mesh_mm with fp64 accumulation, rounded to fp32.  reg set: CSR rr_* [Jr, nv].  input set: CSR ir_* [Ji, nv]
+ *              plus n_mid appended midpoints (a + b) / 2 (add_pelvis_and_neck; `midpoints` is a HOST array [n_mid, 2] of
+ *              input-row indices), J = Ji + n_mid; ir_ptr NULL: the input set IS the reg set (J = Jr, the human36 input).
+ *              The CSR tables are device memory: the CALLER validates 0 <= idx < nv and ptr ascending.
+ *   given      given_reg_cam [B, Jr, 3] (mm) replaces the regressed reg joints (Human36M's annotations, data/Human36M/
+ *              dataset.py:349); before that fit_err[b] = mean_j |(given_j - mean given) - (regressed_j - mean regressed)|
+ *              (get_fitting_error :301-308, for a regressor whose rows sum to 1).  given_reg_img [B, Jr, 2] replaces the
+ *              projected 2D joints when the input set is the reg set.  fit_thr > 0 and fit_err > fit_thr: status bit 1,
+ *              mesh_valid = 0 and, when the input set is not the reg set, lift_valid = 0 (:396-400).
+ *   project    cam2pixel of joint / 1000: x = (X / 1000) / (Z / 1000) * f_x + c_x (focal, princpt [B, 2]).
+ *   targets    mesh = (mesh_mm - reg[reg_root]) / 1000 (metres), reg_pose3d = reg - reg[reg_root], lift = input -
+ *              input[input_root] (mm) (:263-265).
+ *   bbox       get_bbox (tight: min / max of the 2D input joints), process_bbox at aspect W / H (lib/coord_utils.py:21-66).
+ *   affine     get_affine_transform(center, scale, rot, (W, H)) is a similarity, used in closed form: with s = W / bbox_w,
+ *              (c, sn) = cos / sin of rot degrees, d = p - centre:  x' = s (c d_x + sn d_y) + W / 2,  y' = s (c d_y - sn d_x)
+ *              + H / 2.  area = (s tight_w) (s tight_h): the transformed tight box's side lengths (:315-320).
+ *   augment    rot [B] (degrees) and flip [B] int32, each given or NULL = drawn (augm_params, lib/aug_utils.py:98-117) from
+ *              stage 9, joint 0, block 0: flip = flip_enabled and (uniform(word 0) < 0.5); rot = clip(n rot_factor,
+ *              +- 2 rot_factor) with n = sqrt(-2 ln(1 - u(word 1))) cos(2 pi u(word 2)), set to 0 when u(word 3) < 0.5.
+ *   noise      noise_mode P2M_SAMPLE_NOISE_COCO: p2m_pose_noise_coco's scheme on the first 17 joints in place, every joint
+ *              valid (pelvis and neck keep their clean values; needs J >= 17, sigmas [17]); _TABLE: p2m_pose_noise_table's
+ *              on all J joints (tab_mean, tab_std [J, 2], tab_weight [J]); _NONE.  Same stream, same stages as standalone.
+ *   flip       2D: x = W - x - 1, then the pair swaps.  3D (j3d_processing, lib/aug_utils.py:67-83), LIFT TARGET ONLY:
+ *              rotation by -rot about z, pair swaps, x = -x.  The mesh and the reg joints are neither rotated nor flipped:
+ *              that is how the reference trains (data/AMASS/dataset.py:282-284, 301), and it is kept.
+ *              flip_pairs: HOST array [n_pairs, 2], n_pairs <= 16, disjoint.
+ *   normalise  pose2d / (W, H), then per sample and axis (x - mean) / std with the population std (:286-292).
+ * Outputs: pose2d [B, J, 2], mesh [B, nv, 3], lift_pose3d [B, J, 3], reg_pose3d [B, Jr, 3], mesh_valid [B, nv], lift_valid
+ * [B, J], reg_valid [B, Jr] (1 / 0), status [B] int32; optional (NULL: skipped) fit_err [B], kind [B, 17] int8 (coco noise;
+ * not written for a sample with status bit 0), rot_flip [B, 2] (the rot and flip used).
+ *   status bit 0: degenerate bbox (process_bbox would return None), non-finite 2D joints, or a zero std - the sample's
+ *                 outputs are all zero and its masks 0;   bit 1: fit error over the threshold.
+ * workspace: p2m_train_sample_workspace(B) bytes of device memory, 4-byte aligned.
+ * Errors (P2M_ERR_INVALID, nothing launched): NULL state or required pointer, Jr or J = Ji + n_mid outside [1, 32], n_mid
+ * > 4, roots / midpoints / pairs out of range, unknown noise_mode, coco noise with J < 17, W or H <= 0, small workspace. */
+enum { P2M_SAMPLE_NOISE_NONE = 0, P2M_SAMPLE_NOISE_COCO = 1, P2M_SAMPLE_NOISE_TABLE = 2 };
+int64_t p2m_train_sample_workspace(int32_t B);
+int p2m_train_sample(const float* verts, const float* trans, float mesh_scale, const float* focal, const float* princpt,
+                     int32_t B, int32_t nv, const int32_t* rr_ptr, const int32_t* rr_idx, const float* rr_val, int32_t Jr,
+                     int32_t reg_root, const int32_t* ir_ptr, const int32_t* ir_idx, const float* ir_val, int32_t Ji,
+                     const int32_t* midpoints, int32_t n_mid, int32_t input_root, const float* given_reg_cam,
+                     const float* given_reg_img, float fit_thr, const float* rot, const int32_t* flip, float rot_factor,
+                     int32_t flip_enabled, int32_t noise_mode, const float* sigmas, const float* tab_mean,
+                     const float* tab_std, const float* tab_weight, const int32_t* flip_pairs, int32_t n_pairs, float W,
+                     float H, const uint64_t* state, void* workspace, int64_t workspace_bytes, float* pose2d, float* mesh,
+                     float* lift_pose3d, float* reg_pose3d, float* mesh_valid, float* lift_valid, float* reg_valid,
+                     int32_t* status, float* fit_err, int8_t* kind, float* rot_flip, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

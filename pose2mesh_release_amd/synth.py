@@ -135,3 +135,9 @@ def body_model(kind, num_vertex=None, seed=0):
         m["scale"] = 1000.0
     m["checksum"] = body_checksum(m)
     return m
+
+
+# A standing figure in a 288 x 384 crop: x, y of the 17 COCO joints (nose, eyes, ears, shoulders, elbows, wrists, hips, knees,
+# ankles; left first) - the pose of the sample-noise tests and of tools/sample_throughput.py
+COCO_STANDING_POSE = ((144, 60), (150, 54), (138, 54), (158, 58), (130, 58), (175, 100), (113, 100), (190, 150), (98, 150),
+                      (196, 195), (92, 195), (164, 205), (124, 205), (166, 275), (122, 275), (168, 345), (120, 345))
