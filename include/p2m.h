@@ -754,6 +754,66 @@ int p2m_train_sample(const float* verts, const float* trans, float mesh_scale, c
                      float* lift_pose3d, float* reg_pose3d, float* mesh_valid, float* lift_valid, float* reg_valid,
                      int32_t* status, float* fit_err, int8_t* kind, float* rot_flip, void* stream);
 
+/* ---- Rendering: batched z-buffer rasteriser and image overlay (csrc/render.hip) ------------------------------------------
+ * The device counterpart of demo/renderer.py + demo/run.py:46-67 (trimesh, pyrender, OpenGL / EGL, host compositing).  That
+ * code needs an OpenGL context and cannot run where this library is built and tested, so this comment is the contract and
+ * tests/render_ref.py its float64 / exact-integer restatement.  GEOMETRY follows the reference (renderer.py:28-35 the weak-
+ * perspective projection matrix, :68-71 the 180 degree turn about x, :85-91,103-104 the identity camera pose, GL's viewport
+ * and depth test, the top-down read-back): a vertex (x, y, z) of mesh b with cam[b] = (sx, sy, tx, ty) and an H x W image
+ * lands at
+ *   px = W/2 (1 + sx (x + tx)),  py = H/2 (1 + sy (y + ty)),  depth = z   (smaller is nearer; kept for zmin <= depth <= zmax,
+ *                                                                          the reference's clip volume is [-1, 1])
+ * with the centre of pixel (row i, column j) at (j + 0.5, i + 0.5).  A face is front-facing when its normal (v1 - v0) x
+ * (v2 - v0) points to -z in these mesh coordinates; back faces are culled with flag bit 0 (pyrender's default).  SHADING is
+ * this project's, not pyrender's metallic-roughness model: faces are flat-shaded (the reference's smooth=False),
+ *   I = ambient + sum_l k_l max(0, n . l_l),   rgb_c = floor(255 min(1, colour_c I) + 0.5)
+ * with n the unit face normal turned towards the viewer (n_z <= 0), l_l the unit vector towards light l (lights: HOST array
+ * [nl][4] = direction x, y, z and k_l, nl <= 4, normalised in fp64 before the launch), everything in fp64 per face.
+ * Compositing is renderer.py:112-113: a covered pixel shows its face's rgb, every other pixel the background (NULL: zeros).
+ * COVERAGE IS EXACT.  Per mesh, in fp64 on the device, each operation rounded once:
+ *   ax = (W/2) sx,  bx = (W/2) (1 + sx tx),  ay = (H/2) sy,  by = (H/2) (1 + sy ty)
+ *   X = rint(256 fma(ax, x, bx)),  Y = rint(256 fma(ay, y, by))      (ties to even; int32; clamped to +-2^23, status bit 0;
+ *                                                                     a NaN counts as +2^23)
+ * Everything after is integer.  With area2 = (X1 - X0)(Y2 - Y0) - (X2 - X0)(Y1 - Y0): a face with area2 = 0 covers nothing;
+ * it is front-facing iff area2 sgn(ax ay) < 0; s = sgn(area2).  For the edges k = 0: v0 -> v1, 1: v1 -> v2, 2: v2 -> v0
+ * (a -> b) and a pixel centre P = (256 j + 128, 256 i + 128), in int64,
+ *   E_k(P) = A_k (Px - Xa) + B_k (Py - Ya),   A_k = -s (Yb - Ya),   B_k = s (Xb - Xa)        (interior: E_k > 0)
+ * and the pixel is covered iff, for every k, E_k > 0, or E_k = 0 on a left edge (A_k > 0) or a top edge (A_k = 0 and
+ * B_k > 0): the D3D top-left rule, so a mesh is watertight - a centre on a shared edge belongs to exactly one face.
+ * DEPTH at a covered pixel, all in fp32 (conversions and divisions correctly rounded):
+ *   l1 = (float)E_2 / (float)|area2|,  l2 = (float)E_0 / (float)|area2|,  depth = fmaf(l2, z2 - z0, fmaf(l1, z1 - z0, z0))
+ * within 12 x 2^-24 max|z| of the exact plane value (derivation in tests/render_ref.py).  A fragment is kept when
+ * zmin <= depth <= zmax.  The VISIBLE fragment of a pixel is the minimum of a 64-bit key over its fragments,
+ *   batch mode, scene mode with flag bit 1 (depth order):  [order-preserving bits of depth : 32][mesh rank : 8][face id : 24]
+ *   scene mode without it (list order, run.py:311-315):    [255 - mesh rank : 8][the same depth bits : 32][face id : 24]
+ * (rank = the mesh's index in scene mode, 0 in batch mode): nearest first and an exact depth tie to the lower rank, then the
+ * lower face id; in list order a later mesh paints over an earlier one.  The minimum is taken with integer atomics in LDS,
+ * per 64 x 64-pixel tile: no float atomics, bitwise reproducible, a mesh's pixels do not depend on the batch around it.
+ *   verts [B, nv, 3] fp32, faces [nf, 3] int32 (shared by the meshes), cam [B, 4] fp32, colours [B, 3] fp32: device memory
+ *   flags        bit 0 cull back faces, bit 1 depth order (scene mode)
+ *   mode         0 batch: mesh b is rendered into image b (B images);  1 scene: all meshes into one image
+ *   background   uint8 [H, W, 3] (bg_per_mesh = 0) or [B, H, W, 3] (bg_per_mesh = 1, batch mode only) or NULL
+ *   image uint8 [n, H, W, 3], face_id int32 [n, H, W] (-1: background), mesh_id int32 [n, H, W] (the mesh's index b, -1:
+ *   background), depth fp32 [n, H, W] (+inf: background), n = B or 1; each may be NULL
+ *   status       int32 [B] or NULL: bit 0 a snapped coordinate of a referenced vertex was clamped, bit 1 a face index outside
+ *                [0, nv) (that face covers nothing and its vertices are never read)
+ *   workspace    p2m_mesh_render_workspace bytes of device memory, 16-byte aligned
+ * One memset node and two kernels on `stream`: no allocation, no synchronisation, no data-dependent grid (capturable).
+ * p2m_mesh_project: xy_fix [B, nv, 2] = (X, Y) of every vertex, by the same code; status bit 0 as above, over all vertices.
+ * Errors (P2M_ERR_INVALID, nothing launched): NULL required pointers, nf < 1 or nf >= 2^24, more than 255 meshes in scene
+ * mode (65535 in batch mode), H or W outside [1, 8192], nl outside [0, 4], a zero or non-finite light direction, B nf >= 2^31,
+ * unknown mode or flag bits, a per-mesh background in scene mode, a misaligned workspace.                                 */
+enum { P2M_RENDER_BATCH = 0, P2M_RENDER_SCENE = 1 };
+enum { P2M_RENDER_CULL = 1, P2M_RENDER_DEPTH_ORDER = 2 };
+int p2m_mesh_project(const float* verts, const float* cam, int32_t B, int32_t nv, int32_t H, int32_t W, int32_t* xy_fix,
+                     int32_t* status, void* stream);
+int p2m_mesh_render_workspace(int32_t B, int32_t nf, int32_t H, int32_t W, int32_t mode, int64_t* bytes_out);
+int p2m_mesh_render(const float* verts, const int32_t* faces, int32_t nf, const float* cam, const float* colours,
+                    const float* lights, int32_t nl, float ambient, float zmin, float zmax, int32_t flags,
+                    const uint8_t* background, int32_t bg_per_mesh, int32_t B, int32_t nv, int32_t H, int32_t W, int32_t mode,
+                    uint8_t* image, int32_t* face_id, int32_t* mesh_id, float* depth, int32_t* status, void* workspace,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
