@@ -213,3 +213,165 @@ def render_case(c, xy_fix=None):
         ras["proj"] = [proj[b] for b in g]
         out.append(ras)
     return out
+
+
+# ---- the device-exact yardstick ---------------------------------------------------------------------------------------------
+# rasterise() above decides a pixel only where float64 can: it leaves out exact depth ties and fragments within their bound of a
+# clip plane - the pixels where the rules include/p2m.h states bit for bit apply.  rasterise_exact() evaluates the header's own
+# fp32 formula (correctly rounded conversions and divisions, z_k - z0 rounded once, two exactly evaluated fmafs), keeps a fragment
+# when zmin <= depth <= zmax in fp32 and takes the minimum of the header's 64-bit key: every pixel is decided and depth is
+# comparable bitwise.  The two yardsticks check each other in tests/test_render_edges_cpu.py.
+NO_KEY = np.uint64(0xFFFFFFFFFFFFFFFF)
+_TWO128 = 2.0 ** 128
+
+
+def fma32(a, b, c):
+    """fmaf(a, b, c) on float32 arrays, rounded once (Python 3.10 has no math.fma).  The float64 product of two fp32 factors is
+    exact (48 bits, no over- or underflow); a TwoSum gives product + addend exactly as s + e with s the float64 rounding; the
+    fp32 rounding of s is the fp32 rounding of s + e unless s lies exactly half-way between two neighbouring fp32 values and
+    e != 0 (no float64 lies strictly between s + e and s, so they are on the same side of every other boundary): there e
+    decides.  NaN and +-inf come out of the float64 sum as fmaf gives them; an exact zero has the sign of the float64 sum, which
+    is fmaf's."""
+    a, b, c = (np.asarray(v, np.float32) for v in (a, b, c))
+    with np.errstate(all="ignore"):
+        p = a.astype(np.float64) * b.astype(np.float64)
+        c8 = c.astype(np.float64)
+        s = p + c8
+        t = s - p
+        e = (p - (s - t)) + (c8 - t)
+        r = np.asarray(s.astype(np.float32))
+        lo = np.where(r.astype(np.float64) <= s, r, np.nextafter(r, np.float32(-np.inf))).astype(np.float32)
+        hi = np.nextafter(lo, np.float32(np.inf))
+        lo8 = np.where(np.isneginf(lo), -_TWO128, lo.astype(np.float64))      # (the overflow threshold rounds like a value)
+        hi8 = np.where(np.isposinf(hi), _TWO128, hi.astype(np.float64))
+        half = np.isfinite(s) & (lo8 != s) & ((s - lo8) == (hi8 - s)) & (e != 0)
+        r = np.where(half, np.where(e > 0, hi, lo), r)
+    return r.astype(np.float32)
+
+
+def depth_bits(d):
+    """Order-preserving bits of an fp32 depth: smaller float <=> smaller unsigned (-0.0 sorts below +0.0)."""
+    u = np.ascontiguousarray(d, np.float32).view(np.uint32)
+    return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def bits_depth(b):
+    b = np.ascontiguousarray(b, np.uint32)
+    return np.where(b & np.uint32(0x80000000), b & np.uint32(0x7FFFFFFF), ~b).astype(np.uint32).view(np.float32)
+
+
+def pixel_bbox(X, Y, H, W):
+    """Inclusive pixel bbox (jx0, jy0, jx1, jy1) of the centres inside the snapped coordinates' bbox, clipped to the image."""
+    jx0, jx1 = max((int(X.min()) - FIX // 2 + FIX - 1) // FIX, 0), min((int(X.max()) - FIX // 2) // FIX, W - 1)
+    jy0, jy1 = max((int(Y.min()) - FIX // 2 + FIX - 1) // FIX, 0), min((int(Y.max()) - FIX // 2) // FIX, H - 1)
+    return jx0, jy0, jx1, jy1
+
+
+def rasterise_exact(meshes, faces, H, W, cull=True, z_range=(-1.0, 1.0), order="depth", single_faces=None):
+    """rasterise() with depth and the winner as include/p2m.h defines them, in fp32.  Same arguments; per pixel face_id, mesh_id
+    (-1: background), depth (float32, +inf: background), count (fragments kept), on_edge, and for rasterise()'s readers bound
+    (zeros) and left_out (all False: every pixel is decided).  Besides: ties [H, W], the number of kept fragments at the
+    pixel's smallest depth bits (>= 2: an exact depth tie for the front), and kept / dropped, dicts (rank, face) -> covered
+    pixels that passed / failed zmin <= depth <= zmax.  A face with an index outside [0, nv) covers nothing."""
+    zmin, zmax = np.float32(z_range[0]), np.float32(z_range[1])
+    keys = np.full((H, W), NO_KEY, np.uint64)
+    min_db = np.full((H, W), 1 << 32, np.uint64)
+    ties = np.zeros((H, W), np.int32)
+    count = np.zeros((H, W), np.int32)
+    on_edge = np.zeros((H, W), bool)
+    kept, dropped = {}, {}
+    faces = np.asarray(faces, np.int64)
+    ids = np.arange(len(faces)) if single_faces is None else np.asarray(single_faces, np.int64)
+    f4 = np.float32
+    for rank, mesh in enumerate(meshes):
+        xy, z = np.asarray(mesh["xy"], np.int64), np.asarray(mesh["z"], np.float32)
+        sel = ids[((faces[ids] >= 0) & (faces[ids] < len(xy))).all(1)]
+        Xa, Ya = xy[faces[sel], 0], xy[faces[sel], 1]
+        a2 = (Xa[:, 1] - Xa[:, 0]) * (Ya[:, 2] - Ya[:, 0]) - (Xa[:, 2] - Xa[:, 0]) * (Ya[:, 1] - Ya[:, 0])
+        live = a2 != 0
+        if cull:
+            live &= (a2 > 0) if mesh.get("mirror", False) else (a2 < 0)
+        for f in sel[live]:
+            f = int(f)
+            i = faces[f]
+            X, Y = xy[i, 0], xy[i, 1]
+            area2 = int((X[1] - X[0]) * (Y[2] - Y[0]) - (X[2] - X[0]) * (Y[1] - Y[0]))
+            s = 1 if area2 > 0 else -1
+            jx0, jy0, jx1, jy1 = pixel_bbox(X, Y, H, W)
+            if jx0 > jx1 or jy0 > jy1:
+                continue
+            Px = (np.arange(jx0, jx1 + 1, dtype=np.int64) * FIX + FIX // 2)[None, :]
+            Py = (np.arange(jy0, jy1 + 1, dtype=np.int64) * FIX + FIX // 2)[:, None]
+            inside = np.ones((jy1 - jy0 + 1, jx1 - jx0 + 1), bool)
+            closed = inside.copy()
+            E = []
+            for k in range(3):
+                a, b = k, (k + 1) % 3
+                A, Bc = -s * (Y[b] - Y[a]), s * (X[b] - X[a])
+                Ek = A * (Px - X[a]) + Bc * (Py - Y[a])
+                inside &= (Ek > 0) | ((Ek == 0) & bool(A > 0 or (A == 0 and Bc > 0)))
+                closed &= Ek >= 0
+                E.append(Ek)
+            win = (slice(jy0, jy1 + 1), slice(jx0, jx1 + 1))
+            on_edge[win] |= closed & ((E[0] == 0) | (E[1] == 0) | (E[2] == 0))
+            if not inside.any():
+                continue
+            with np.errstate(all="ignore"):
+                area = np.int64(s * area2).astype(f4)
+                l1, l2 = E[2].astype(f4) / area, E[0].astype(f4) / area
+                z0, d1, d2 = z[i[0]], f4(z[i[1]] - z[i[0]]), f4(z[i[2]] - z[i[0]])
+                d = fma32(l2, d2, fma32(l1, d1, z0))
+                keep = inside & (d >= zmin) & (d <= zmax)
+            kept[(rank, f)], dropped[(rank, f)] = int(keep.sum()), int((inside & ~keep).sum())
+            if not keep.any():
+                continue
+            db = depth_bits(d).astype(np.uint64)
+            if order == "list":
+                key = (np.uint64(255 - rank) << np.uint64(56)) | (db << np.uint64(24)) | np.uint64(f)
+            else:
+                key = (db << np.uint64(32)) | (np.uint64(rank) << np.uint64(24)) | np.uint64(f)
+            keys[win] = np.minimum(keys[win], np.where(keep, key, NO_KEY))
+            mb, t = min_db[win], ties[win]
+            lt, eq = keep & (db < mb), keep & (db == mb)
+            ties[win] = np.where(lt, 1, np.where(eq, t + 1, t))
+            min_db[win] = np.where(lt, db, mb)
+            count[win] += keep
+    covered = keys != NO_KEY
+    if order == "list":
+        rk, db = np.uint64(255) - (keys >> np.uint64(56)), (keys >> np.uint64(24)) & np.uint64(0xFFFFFFFF)
+    else:
+        rk, db = (keys >> np.uint64(24)) & np.uint64(0xFF), keys >> np.uint64(32)
+    face_id = np.where(covered, (keys & np.uint64(0xFFFFFF)).astype(np.int64), -1).astype(np.int32)
+    mesh_id = np.where(covered, rk.astype(np.int64), -1).astype(np.int32)
+    depth = np.where(covered, bits_depth(db.astype(np.uint32)), f4(np.inf)).astype(f4)
+    return dict(face_id=face_id, mesh_id=mesh_id, depth=depth, bound=np.zeros((H, W)), count=count,
+                left_out=np.zeros((H, W), bool), on_edge=on_edge, ties=ties, kept=kept, dropped=dropped)
+
+
+def render_case_exact(c, xy_fix=None):
+    """render_case() on rasterise_exact(): a case of tests/render_cases.py or tests/render_edge_cases.py -> list over images.
+    A case may name `single_faces` (the only faces that can cover anything: keeps the host loop short at a large nf); faces
+    with an index outside [0, nv) cover nothing and are shaded as face (0, 0, 0), which is never seen."""
+    B, H, W = c["verts"].shape[0], c["H"], c["W"]
+    nv = c["verts"].shape[1]
+    proj = [project(c["verts"][b], c["cam"][b], H, W) for b in range(B)]
+    meshes = [dict(xy=proj[b]["xy"] if xy_fix is None else np.asarray(xy_fix[b], np.int64), z=c["verts"][b][:, 2],
+                   mirror=proj[b]["mirror"]) for b in range(B)]
+    valid = ((c["faces"] >= 0) & (c["faces"] < nv)).all(1)
+    safe = np.where(valid[:, None], c["faces"], 0)
+    with np.errstate(all="ignore"):
+        vals = [face_values(c["verts"][b], safe, c["colours"][b], c["lights"], c["ambient"]) for b in range(B)]
+    groups = [list(range(B))] if c["mode"] == "scene" else [[b] for b in range(B)]
+    out = []
+    for g in groups:
+        ras = rasterise_exact([meshes[b] for b in g], c["faces"], H, W, c["cull"], c["z_range"],
+                              c["order"] if c["mode"] == "scene" else "depth", c.get("single_faces"))
+        bg = c["background"]
+        if bg is not None and bg.ndim == 4:
+            bg = bg[g[0]]
+        ras["image"], ras["v"] = shade(ras, [vals[b] for b in g], bg, H, W)
+        if c["mode"] != "scene":
+            ras["mesh_id"] = np.where(ras["mesh_id"] >= 0, g[0], -1).astype(np.int32)
+        ras["proj"] = [proj[b] for b in g]
+        out.append(ras)
+    return out

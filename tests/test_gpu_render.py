@@ -24,10 +24,11 @@ GUARD = 256
 class Guarded:
     """A device array of `shape` inside a buffer with GUARD sentinel elements on both sides, everything pre-filled."""
 
-    def __init__(self, shape, dtype, fill):
+    def __init__(self, shape, dtype, fill, offset=0):
         n = int(np.prod(shape))
-        self.buf = torch.full((n + 2 * GUARD,), fill, dtype=dtype, device="cuda")
-        self.view = self.buf[GUARD:GUARD + n].view(*shape)
+        self.buf = torch.full((n + 2 * GUARD + offset,), fill, dtype=dtype, device="cuda")
+        self.lo = GUARD + offset                                # (offset: elements by which the array is pushed off 16 bytes)
+        self.view = self.buf[self.lo:self.lo + n].view(*shape)
         self.fill = fill
 
     def ptr(self):
@@ -37,7 +38,7 @@ class Guarded:
         return bool(torch.isnan(t).all()) if isinstance(self.fill, float) else bool((t == self.fill).all())
 
     def guards_ok(self):
-        return self.untouched(self.buf[:GUARD]) and self.untouched(self.buf[-GUARD:])
+        return self.untouched(self.buf[:self.lo]) and self.untouched(self.buf[self.lo + self.view.numel():])
 
 
 def _p(t):
@@ -60,8 +61,10 @@ def abi_project(c):
     return xy.view.cpu().numpy(), st.view.cpu().numpy()
 
 
-def abi_render(c, want=("image", "face_id", "mesh_id", "depth", "status"), expect_rc=0, **over):
-    """p2m_mesh_render on a case dict with guarded, pre-filled outputs -> (rc, dict of numpy results, guarded)."""
+def abi_render(c, want=("image", "face_id", "mesh_id", "depth", "status"), expect_rc=0, offset=None, **over):
+    """p2m_mesh_render on a case dict with guarded, pre-filled outputs -> (rc, dict of numpy results, guarded).  offset: {output
+    name or "background": elements by which that array starts behind a 16-byte boundary}."""
+    offset = offset or {}
     from pose2mesh_release_amd import _lib
     lib = _lib.hip()
     c = dict(c, **over)
@@ -73,11 +76,15 @@ def abi_render(c, want=("image", "face_id", "mesh_id", "depth", "status"), expec
     scene = c["mode"] == "scene"
     n = 1 if scene else B
     bg = None if c["background"] is None else torch.from_numpy(c["background"]).cuda()
+    if bg is not None and offset.get("background"):
+        room = torch.zeros(bg.numel() + offset["background"], dtype=torch.uint8, device="cuda")
+        room[offset["background"]:] = bg.reshape(-1)
+        bg = room[offset["background"]:].view(bg.shape)
     per = 1 if bg is not None and bg.dim() == 4 else 0
-    g = {"image": Guarded((n, max(H, 1), max(W, 1), 3), torch.uint8, 0x5A),
-         "face_id": Guarded((n, max(H, 1), max(W, 1)), torch.int32, -77),
-         "mesh_id": Guarded((n, max(H, 1), max(W, 1)), torch.int32, -77),
-         "depth": Guarded((n, max(H, 1), max(W, 1)), torch.float32, float("nan")),
+    g = {"image": Guarded((n, max(H, 1), max(W, 1), 3), torch.uint8, 0x5A, offset.get("image", 0)),
+         "face_id": Guarded((n, max(H, 1), max(W, 1)), torch.int32, -77, offset.get("face_id", 0)),
+         "mesh_id": Guarded((n, max(H, 1), max(W, 1)), torch.int32, -77, offset.get("mesh_id", 0)),
+         "depth": Guarded((n, max(H, 1), max(W, 1)), torch.float32, float("nan"), offset.get("depth", 0)),
          "status": Guarded((B,), torch.int32, -77)}
     nb = ct.c_int64(-1)
     rcw = lib.p2m_mesh_render_workspace(B, nf, H, W, 1 if scene else 0, ct.byref(nb))
