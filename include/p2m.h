@@ -662,6 +662,7 @@ int p2m_body_forward(const float* pose, const float* pose_mean, const float* bet
  *   7 select      block 0: word 0 the miss-source uniform, word 1 the category uniform
  *   8 table       block 0: word 0 the Bernoulli uniform, words 1, 2 the Box-Muller pair (u0, u1)
  *   9 augment     joint 0, block 0: word 0 flip, words 1, 2 the rotation's Box-Muller pair, word 3 rot = 0 (p2m_train_sample)
+ *  10 camera start   joint 0, block 0: words 0, 1, 2 the start (s, tx, ty) of the camera fit (p2m_camera_fit)
  * with ks_q = sqrt(area) 2 sigma_j sqrt(-2 ln q) (get_dist_wrt_ks, lib/noise_utils.py:18-24; a negative or NaN area counts
  * as 0).  tests/sample_ref.py mirrors all of this in numpy, float64.
  *
@@ -813,6 +814,73 @@ int p2m_mesh_render(const float* verts, const int32_t* faces, int32_t nf, const 
                     const uint8_t* background, int32_t bg_per_mesh, int32_t B, int32_t nv, int32_t H, int32_t W, int32_t mode,
                     uint8_t* image, int32_t* face_id, int32_t* mesh_id, float* depth, int32_t* status, void* workspace,
                     void* stream);
+
+/* ---- The demo's camera: batched 2D-pose preparation and the L1 Adam fit (csrc/camfit.hip) ---------------------------------
+ * The piece of demo/run.py between its two device halves (optimize_cam_param, :149-197): pixels of 2D joints -> the network's
+ * input and the fit's target (p2m_pose_prepare); 3D joints + target -> the weak-perspective camera of the crop
+ * (p2m_camera_fit).  One launch each on `stream`, no allocation, no synchronisation (capturable).  tests/camfit_ref.py restates
+ * both in numpy, float64.
+ *
+ * p2m_pose_prepare: run.py:150-159 for a batch.  joints [B, J, 2] fp32, pixels of the original image; in_W, in_H the network's
+ *   input shape (288 x 384 for the bodies); crop the side of the virtual crop (500 in the demo).  One wave per sample, lane j =
+ *   joint j, fp32, each operation rounded once and none fused:
+ *     tight    (x0, y0, tw, th) = (min x, min y, max x - min x, max y - min y)                 (get_bbox, coord_utils.py:21-39)
+ *     box(aspect, scale)  w = tw - 1, h = th - 1;  cx = x0 + w / 2, cy = y0 + h / 2;  w > aspect h: h = w / aspect;
+ *              w < aspect h: w = h aspect;  w = w scale, h = h scale                           (process_bbox, :42-66)
+ *     bbox2 = box(in_W / in_H, 1.0),  bbox1 = box(1, 1.25); both share the centre (cx, cy)
+ *     affine   the rot = 0 similarity of get_affine_transform in closed form, as in p2m_train_sample: with s = res_w / bbox_w,
+ *              x' = s (x - cx) + res_w / 2,  y' = s (y - cy) + res_h / 2
+ *     target   = affine of (crop, crop) with bbox1;   p = affine of (in_W, in_H) with bbox2, then p / (in_W, in_H)
+ *     pose2d   = (p - mean) / std per sample and axis, the population std; sums over the lanes in the butterfly order below
+ *     bbox     = (cx - w1 / 2, cy - h1 / 2, w1, h1): the reference's bbox1, what crop_cam_to_image takes
+ *   status [B] int32, bit 0 as p2m_train_sample's: a degenerate box (tw th <= 0, tw < 1 or th < 1: process_bbox would return
+ *   None), a non-finite joint, a zero or non-finite std.  That sample's pose2d, target and bbox are then all zero.
+ *   Inputs are float.  The reference's demo file is int64, and aug_utils.py:59 writes the transformed points back into that
+ *   integer array, truncating them: a property of that fixture (kept in oracle/demo_oracle.py), not of this entry point.
+ *   Errors (P2M_ERR_INVALID, nothing launched): NULL pointers, B < 1, J outside [1, 64], in_W, in_H or crop not in (0, 1e6).
+ *
+ * p2m_camera_fit: OptimzeCamLayer (lib/models/project_net.py:7-17) + nn.L1Loss + torch.optim.Adam + the rate steps of
+ *   run.py:176-189, for B independent samples.  One wave per sample, lane j holds joint j for the whole fit.
+ *     joints3d [B, J, 3] fp32 (only x, y are read), target [B, J, 2], weight [B, J] or NULL (w_j = 1), cam0 [B, 3] or NULL,
+ *     state: the two device words {seed, first_index} of the noise stream (may be NULL when cam0 is given), sched: at most 8
+ *     (first_step, lr) pairs by value, first_step[0] = 0 and strictly ascending: step i (zero-based) runs at the lr of the last
+ *     entry with first_step <= i.  The reference lowers the rate AFTER the steps with j == 500 and j == 1000, so its schedule
+ *     is ((0, 0.1), (501, 0.05), (1001, 0.001)) with steps = 1500.  img_res = crop / 2.
+ *   All arithmetic is fp32, each operation rounded once and none fused (no fma), except where fp64 is named.
+ *   SUMS over the joints are taken over the wave's 64 lanes (lanes >= J hold +0) in ONE fixed butterfly order:
+ *     v1[l] = v[l] + v[l ^ 1],  v2[l] = v1[l] + v1[l ^ 2],  v4[l] = v2[l] + v2[l ^ 4],  ..,  v32[l] = v16[l] + v16[l ^ 32]
+ *   fp32 addition commutes, so every lane ends with the same bits, and a sample's result depends on the sample alone.
+ *   Setup:   W = sum_j w_j,  c_j = (w_j / (2 W)) r   (r = img_res);  cam = cam0[b], or drawn (below)
+ *   Step t = 1 .. steps, with (s, tx, ty) = cam:
+ *     q_j = (x_j + tx, y_j + ty),  pred_j = (q_j s) r + r        (the module's order),   e_j = pred_j - t_j
+ *     g_j = sign(e_j) c_j per axis, sign(0) = 0 (torch's)
+ *     grad = (sum_j (g_jx q_jx + g_jy q_jy),  sum_j g_jx s,  sum_j g_jy s)                    three butterfly sums
+ *     m = m + (grad - m) (float)(1 - beta1)                                                   (lerp_)
+ *     v = v (float)beta2 + ((float)(1 - beta2) grad) grad                                     (mul_, addcmul_)
+ *     cam = cam - (step_size_t m) / (sqrt(v) / c2_t + (float)eps)                             (addcdiv_)
+ *     step_size_t = (float)(lr_t / (1 - beta1^t)),  c2_t = (float)sqrt(1 - beta2^t): torch computes the two corrections in
+ *     float64 on the host with pow(); HERE beta1^t and beta2^t are running fp64 products on the device (one multiply per
+ *     step), the division and square root are fp64, and each is rounded to fp32 once per step.
+ *   Outputs: cam [B, 3] after the last step; loss [B] = (sum_j w_j (|e_jx| + |e_jy|)) / (2 W), evaluated once more at exactly
+ *   those parameters (one butterfly sum of the lane terms w_j (|e_jx| + |e_jy|)); steps = 0 returns the start bitwise.
+ *   Start: with cam0 NULL the reference's torch.rand((1, 3)) is drawn from the project's one Philox stream as
+ *     stage 10 "camera start", joint 0, block 0: (s, tx, ty) = words 0, 1, 2 as (word >> 8) 2^-24, counter = the global sample
+ *     index state[1] + b  (stages 0-9: "training-sample noise" above).  The caller advances state[1] by B with a tensor add.
+ *   status [B] int32: bit 0 a non-finite value among the sample's x, y, target, weights or start, or W <= 0: cam = 0, loss = 0,
+ *   the other samples are untouched;  bit 1: s <= 0 at the end (the mirrored solution; reported, not altered).
+ *   Errors (P2M_ERR_INVALID, nothing launched): NULL required pointers, both cam0 and state NULL, misaligned state, B < 1, J
+ *   outside [1, 64], steps outside [0, 65535], sched.n outside [1, 8], first_step[0] != 0 or not strictly ascending, an lr
+ *   that is not finite, img_res <= 0 or not finite, betas outside [0, 1), eps < 0.                                         */
+typedef struct p2m_fit_schedule {
+  int32_t n;
+  int32_t first_step[8];
+  double lr[8];
+} p2m_fit_schedule;
+int p2m_pose_prepare(const float* joints, int32_t B, int32_t J, float in_W, float in_H, float crop, float* pose2d, float* target,
+                     float* bbox, int32_t* status, void* stream);
+int p2m_camera_fit(const float* joints3d, const float* target, const float* weight, const float* cam0, const uint64_t* state,
+                   int32_t B, int32_t J, p2m_fit_schedule sched, int32_t steps, float img_res, double beta1, double beta2,
+                   double eps, float* cam, float* loss, int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,13 @@ class P2MError(RuntimeError):
 
 
 _c = ctypes
-_i32, _i64, _f32, _vp = _c.c_int32, _c.c_int64, _c.c_float, _c.c_void_p
+_i32, _i64, _f32, _f64, _vp = _c.c_int32, _c.c_int64, _c.c_float, _c.c_double, _c.c_void_p
+
+
+class FitSchedule(_c.Structure):
+    """p2m_fit_schedule of include/p2m.h: at most 8 (first_step, lr) pairs, passed by value."""
+    _fields_ = [("n", _i32), ("first_step", _i32 * 8), ("lr", _f64 * 8)]
+
 
 # name -> (restype, argtypes); must list every symbol of include/p2m.h (tests check this)
 HIP_SYMBOLS = {
@@ -128,6 +134,9 @@ HIP_SYMBOLS = {
     "p2m_mesh_render_workspace": (_c.c_int, [_i32, _i32, _i32, _i32, _i32, _c.POINTER(_i64)]),
     "p2m_mesh_render": (_c.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _i32, _vp, _i32, _i32, _i32, _i32,
                                    _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "p2m_pose_prepare": (_c.c_int, [_vp, _i32, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "p2m_camera_fit": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, FitSchedule, _i32, _f32, _f64, _f64, _f64, _vp, _vp, _vp,
+                                  _vp]),
 }
 
 HOST_SYMBOLS = {
