@@ -1,6 +1,7 @@
 // Dense contractions of the Pose2Mesh Chebyshev GCN on gfx950 matrix cores.
 //
 //   k_gemm_planes[_bx|_ws] : C = [A0|A1|A2] * Bm + bias  (+ addend / un-pool pair-sum, BatchNorm partials in the epilogue)
+//   k_gemm_rows_k1         : the row-set form of the above with one A plane and Ka <= 256, slice arithmetics: whole-K tile, no ring
 //   k_gemm_tn[_bx|_ws]     : P[chunk] = [A0|A1|A2]^T * G  over a chunk of rows (weight gradient)
 //   k_naive_*              : scalar fall-backs for the odd shapes (Fin=5 first conv, Fout=3 last conv)
 //
@@ -627,6 +628,229 @@ __global__ __launch_bounds__(512, (BN == 128 && ROWS) ? 4 : 2) void k_gemm_plane
       __syncthreads();
     }
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_gemm_rows_k1: the row-set contraction with ONE A plane and Ka <= 256 in the slice arithmetics (the class-representative
+// convs of the split levels, forward and dX, and the two projections of the final conv).  k_gemm_planes_ws was shaped for
+// K = 3 Ka = 384 .. 768: at 2 .. 16 chunks its ring is prologue and drain, with at most 16 KB of A in flight per block.  Here:
+//   * 4 waves, every one loads, splits AND multiplies; no chunk ring.  K is walked in passes of KP = 64 (32 when Ka is no
+//     multiple of 64) columns; the loads of two passes - the whole K up to Ka = 128 - are requested before anything waits,
+//     32 .. 64 KB in flight per block, and pass p + 2 is requested as soon as pass p sits in LDS;
+//   * LDS holds one slice image of the A tile (activation on load and the split applied on the way in), NS x 128 x (KP + 8)
+//     (row stride 36 / 20 dwords: conflict-free ds_read_b128 fragments and, KP = 32 with its row permutation, ds_write_b64);
+//   * B fragments come from the pre-split image (p2m_weight_split layout) straight into registers, one k step ahead: the
+//     weight is <= 256 x 256 and L2-resident, and the fragment a lane needs is 16 contiguous bytes of it;
+//   * one LDS barrier between "image stored" and "MFMAs", one before the image is overwritten;
+//   * a wave whose columns all lie beyond N (the 64-wide tile of N = 32) skips its B loads and MFMAs: nothing of them is stored.
+// 256 threads and launch bound 2 = two blocks per CU at up to 256 registers: no spill, the epilogue included.
+// Results are BITWISE those of k_gemm_planes_ws: k ascending in steps of 16, the same product order per accumulator, the same
+// accumulator -> (row, column) mapping, the same tile -> rows mapping, and gemm_epilogue itself.
+// ---------------------------------------------------------------------------------------------
+#ifdef P2M_K1_TRACE
+// probe build (tools/k1_trace.sh, tools/probes/rows_k1_probe.py): s_memtime stamps of thread 0 of the first 4096 blocks -
+// 0 start, 1 first image stored (row table, first loads, split), 2 k loop done, 3 epilogue done
+__device__ unsigned long long g_k1_tr[4096][4];
+#define P2M_K1T(ev)                                                                      \
+  do {                                                                                   \
+    if (threadIdx.x == 0 && blockIdx.x < 4096) g_k1_tr[blockIdx.x][ev] = __builtin_amdgcn_s_memtime(); \
+  } while (0)
+#else
+#define P2M_K1T(ev) do { } while (0)
+#endif
+
+template <int BN, bool EXTRA, int NS, int KP>
+__global__ __launch_bounds__(256, 2) void k_gemm_rows_k1(GemmArgs g) {
+  typedef typename SliceFrag<NS>::type frag_t;
+  constexpr bool ROWS = true;
+  constexpr int WTN = BN / 2;
+  constexpr int TN = WTN / 32;
+  constexpr int TM = 2;
+  constexpr int LDX = KP + 8;
+  constexpr int TPR = KP / 4;             // threads per row (one float4 each)
+  constexpr int RPS = 256 / TPR;          // rows per sweep of the block
+  constexpr int NSW = BM / RPS;           // sweeps = float4 loads per thread and pass
+  constexpr int KSTEPS = KP / 16;         // MFMA k steps per pass (2 or 4: the B double buffer's parity is static)
+  constexpr int A_IMG = NS * BM * LDX;    // bf16 / fp16 elements
+  static_assert(KP == 64 || KP == 32, "pass width");
+  static_assert(A_IMG / 2 >= 2 * BN, "the epilogue's reduction buffer lives in the image");
+  __shared__ __attribute__((aligned(16))) float smem[A_IMG / 2 + ROWTAB_WORDS];
+  __shared__ __attribute__((aligned(16))) float actco[2 * 256];
+  unsigned short* As = reinterpret_cast<unsigned short*>(smem);
+  int* rowtab = reinterpret_cast<int*>(smem + A_IMG / 2);
+
+  int mt, nt;
+  if (!tile_of_block(blockIdx.x, g.ntm, g.ntn, mt, nt)) return;
+  P2M_K1T(0);
+  const int t = threadIdx.x;
+  const long m0 = (long)mt * BM;
+  const int n0 = nt * BN;
+  const int rs_b = mt / g.tps;
+  const int rs_i0 = (mt - rs_b * g.tps) * BM;
+  const int lane = t & 63, wave = t >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int l31 = lane & 31, lhi = lane >> 5;
+  const int npass = g.Ka / KP;
+  const bool in_act = g.in_scale != nullptr;                             // block-uniform
+  const bool live = n0 + wn * WTN < g.N;                                  // wave-uniform
+  float a_sc = 1.f;
+  int descale = 0;
+  if (NS == 2) {
+    const int sa = slice_scale_exp(*g.a_amax, g.a_bits);
+    a_sc = exp2_int(sa);
+    descale = -(sa + slice_scale_exp(*g.b_amax, 0));
+  }
+
+  // the small tables first (their loads are older than the A loads: filling LDS from them waits for nothing else)
+  int rt_row = -1;
+  float rt_w = 0.f, co_sc = 0.f, co_sh = 0.f;
+  if (t < BM) {
+    const int i = rs_i0 + t;
+    if (i < g.nset) {
+      rt_row = rs_b * g.V + g.ids[i];
+      if (g.row_w != nullptr) rt_w = g.row_w[i];
+    }
+  }
+  if (in_act && t < g.Ka) {
+    co_sc = g.in_scale[t];
+    co_sh = g.in_shift[t];
+  }
+
+  // A addresses: wave-uniform 64-bit base + a 32-bit byte offset per thread and sweep, fixed for the kernel; rows past the
+  // set re-read its last row (their accumulators are dropped by the epilogue)
+  const int a_g = t / TPR;                                               // row group of the thread inside a sweep
+  const int a_row = KP == 64 ? a_g : (((a_g & 1) << 2) | ((a_g >> 1) & 3) | ((a_g >> 3) << 3));
+  const int a_k4 = (t % TPR) * 4;
+  const long sbase0 = (((long)rs_b * g.V) >> g.a0_shift) * g.Ka;         // V is even whenever a0_shift = 1
+  unsigned voff[NSW];
+#pragma unroll
+  for (int ps = 0; ps < NSW; ps++) {
+    int i = rs_i0 + ps * RPS + a_row;
+    if (i >= g.nset) i = g.nset - 1;
+    voff[ps] = (unsigned)((((g.ids[i] >> g.a0_shift) * g.Ka) + a_k4) * 4);
+  }
+  f32x4 ra[2][NSW];
+  auto load_pass = [&](int p, f32x4 (&a)[NSW]) {
+    const char* Ab = reinterpret_cast<const char*>(g.A[0] + sbase0 + p * KP);                        // uniform
+#pragma unroll
+    for (int ps = 0; ps < NSW; ps++) a[ps] = *reinterpret_cast<const f32x4*>(Ab + voff[ps]);
+  };
+  auto store_pass = [&](int p, f32x4 (&a)[NSW]) {
+    if (in_act) {                          // BatchNorm + ReLU of the previous conv on load
+      const f32x4 sc = *reinterpret_cast<const f32x4*>(&actco[p * KP + a_k4]);
+      const f32x4 sh = *reinterpret_cast<const f32x4*>(&actco[256 + p * KP + a_k4]);
+#pragma unroll
+      for (int ps = 0; ps < NSW; ps++)
+#pragma unroll
+        for (int e = 0; e < 4; e++) a[ps][e] = fmaxf(fmaf(a[ps][e], sc[e], sh[e]), 0.f);
+    }
+#pragma unroll
+    for (int ps = 0; ps < NSW; ps++) {
+      u32x2 sl[NS];
+      split_pack4<NS>(a[ps][0], a[ps][1], a[ps][2], a[ps][3], a_sc, sl);
+      unsigned short* d = As + (ps * RPS + a_row) * LDX + a_k4;
+#pragma unroll
+      for (int q = 0; q < NS; q++) *reinterpret_cast<u32x2*>(d + q * BM * LDX) = sl[q];
+    }
+  };
+
+  load_pass(0, ra[0]);
+  if (npass > 1) load_pass(1, ra[1]);                                  // block-uniform
+
+  // B fragments of k step kc (16 rows of the weight): Bx[kc][slice][n][16], 16 bytes per lane
+  const long bx_slice = (long)g.Npad * 16;
+  const int nsteps = g.Ka / 16;
+  unsigned bx_voff[TN];
+#pragma unroll
+  for (int j = 0; j < TN; j++) bx_voff[j] = (unsigned)((((n0 + wn * WTN + j * 32 + l31) * 16) + lhi * 8) * 2);
+  frag_t fb[2][NS][TN];
+  auto load_b = [&](int kc, frag_t (&b)[NS][TN]) {
+    const char* src0 = reinterpret_cast<const char*>(g.Bx + (long)kc * (NS * bx_slice));              // uniform
+#pragma unroll
+    for (int sl = 0; sl < NS; sl++)
+#pragma unroll
+      for (int j = 0; j < TN; j++)
+        b[sl][j] = __builtin_bit_cast(frag_t, *reinterpret_cast<const u32x4*>(src0 + sl * 2 * bx_slice + bx_voff[j]));
+  };
+  if (live) load_b(0, fb[0]);
+
+  if (t < BM) {
+    rowtab[t] = rt_row;
+    if (g.row_w != nullptr) {              // rows_weights_fill, from the value already loaded
+      float* wtab = reinterpret_cast<float*>(rowtab + BM);
+      wtab[t] = rt_w;
+      float s = rt_w;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+      if ((t & 63) == 0) wtab[BM + (t >> 6)] = s;
+    }
+  }
+  if (in_act) {
+    if (t < g.Ka) {
+      actco[t] = co_sc;
+      actco[256 + t] = co_sh;
+    }
+    lds_block_barrier();
+  }
+
+  floatx16 acc[TM][TN];
+#pragma unroll
+  for (int i = 0; i < TM; i++)
+#pragma unroll
+    for (int j = 0; j < TN; j++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
+
+  auto mfma_pass = [&](int p) {
+    const unsigned short* as = As + (wm * 64 + l31) * LDX + lhi * 8;
+#pragma unroll
+    for (int ks = 0; ks < KSTEPS; ks++) {
+      const int kc = p * KSTEPS + ks;
+      frag_t fa[NS][TM];
+#pragma unroll
+      for (int sl = 0; sl < NS; sl++)
+#pragma unroll
+        for (int i = 0; i < TM; i++)
+          fa[sl][i] = __builtin_bit_cast(frag_t, *reinterpret_cast<const u32x4*>(as + (sl * BM + i * 32) * LDX + ks * 16));
+      frag_t (&b)[NS][TN] = fb[ks & 1];
+      load_b(kc + 1 < nsteps ? kc + 1 : kc, fb[(ks + 1) & 1]);            // one step ahead (the last one re-reads itself)
+#define P2M_PAIR(SA, SB)                                                                       \
+  _Pragma("unroll") for (int i = 0; i < TM; i++) _Pragma("unroll") for (int j = 0; j < TN; j++) \
+      acc[i][j] = slice_mfma<NS>(fa[SA][i], b[SB][j], acc[i][j]);
+      if constexpr (NS == 3) {          // smallest products first
+        P2M_PAIR(2, 0)
+        P2M_PAIR(0, 2)
+        P2M_PAIR(1, 1)
+        P2M_PAIR(1, 0)
+        P2M_PAIR(0, 1)
+        P2M_PAIR(0, 0)
+      } else {
+        P2M_PAIR(1, 0)
+        P2M_PAIR(0, 1)
+        P2M_PAIR(0, 0)
+      }
+#undef P2M_PAIR
+    }
+  };
+
+  for (int p = 0; p < npass; p += 2) {
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      const int pp = p + h;
+      if (pp < npass) {                                                   // block-uniform
+        if (pp > 0) lds_block_barrier();                                  // every wave is done with the previous image
+        store_pass(pp, ra[h]);
+        if (pp + 2 < npass) load_pass(pp + 2, ra[h]);
+        lds_block_barrier();
+        if (pp == 0) P2M_K1T(1);
+        if (live) mfma_pass(pp);
+      }
+    }
+  }
+  P2M_K1T(2);
+  __syncthreads();   // the image is free: the epilogue's reduction reuses it
+  gemm_epilogue<BN, EXTRA, ROWS>(g, acc, smem, rowtab, mt, m0, n0, rs_i0, wm, wn, l31, lhi, descale);
+  P2M_K1T(3);
 }
 
 // Bx[k / 16][s][n][k % 16] = s-th bf16 slice of Bm[k][n] (zero for N <= n < Npad): the pre-split weight operand,
@@ -1719,11 +1943,34 @@ extern "C" int p2m_amax_rows(p2m_graph_t gh, int32_t row_set, const float* x, in
 
 // picks the instantiation: tile width from N, EXTRA epilogue, native f32 MFMA or slices (g.Bx != nullptr; two fp16
 // slices when g.a_amax is set)
+// P2M_ROWS_K1 (read once per process): 1 (default) = row-set launches with one A plane and Ka <= 256
+// in the slice arithmetics (both) take k_gemm_rows_k1; 0 = k_gemm_planes_ws as before - the A/B switch, bitwise the same results.
+static bool rows_k1() {
+  static const bool v = [] { const char* e = getenv("P2M_ROWS_K1"); return e ? atoi(e) != 0 : true; }();
+  return v;
+}
+
 template <bool ROWS>
 static void launch_gemm_planes(GemmArgs& g, bool extra, hipStream_t s) {
   const bool wide = (g.N % 128 == 0);
   g.ntn = wide ? g.N / 128 : cdiv(g.N, 64);
   const dim3 grid(cdiv(g.ntm, 8) * 8 * g.ntn);
+  if constexpr (ROWS) {
+    if (g.nplanesA == 1 && g.Ka <= 256 && g.Bx != nullptr && rows_k1()) {
+#define P2M_LAUNCH_K1(BNv, EX, KPv)                                                                          \
+  do {                                                                                                      \
+    if (g.a_amax != nullptr) hipLaunchKernelGGL((k_gemm_rows_k1<BNv, EX, 2, KPv>), grid, dim3(256), 0, s, g); \
+    else hipLaunchKernelGGL((k_gemm_rows_k1<BNv, EX, 3, KPv>), grid, dim3(256), 0, s, g);                    \
+  } while (0)
+#define P2M_LAUNCH_K1_KP(BNv, EX) \
+  do { if (g.Ka % 64 == 0) P2M_LAUNCH_K1(BNv, EX, 64); else P2M_LAUNCH_K1(BNv, EX, 32); } while (0)
+      if (wide) { if (extra) P2M_LAUNCH_K1_KP(128, true); else P2M_LAUNCH_K1_KP(128, false); }
+      else { if (extra) P2M_LAUNCH_K1_KP(64, true); else P2M_LAUNCH_K1_KP(64, false); }
+#undef P2M_LAUNCH_K1_KP
+#undef P2M_LAUNCH_K1
+      return;
+    }
+  }
   if (g.Bx != nullptr) {
 #define P2M_LAUNCH_WS(BNv, EX)                                                                              \
   do {                                                                                                      \
@@ -2033,6 +2280,13 @@ extern "C" int p2m_weight_grad_unpack(const float* P, const float* Pdb, int32_t 
 extern "C" int p2m_tn_trace_dump(unsigned long long* out /* [8][32][4] host */) {
   if (hipDeviceSynchronize() != hipSuccess) return P2M_ERR_HIP;
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(p2m::g_tn_tr), sizeof(unsigned long long) * 8 * 32 * 4) == hipSuccess ? P2M_OK
+                                                                                                                : P2M_ERR_HIP;
+}
+#endif
+#ifdef P2M_K1_TRACE
+extern "C" int p2m_k1_trace_dump(unsigned long long* out /* [4096][4] host */) {
+  if (hipDeviceSynchronize() != hipSuccess) return P2M_ERR_HIP;
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(p2m::g_k1_tr), sizeof(unsigned long long) * 4096 * 4) == hipSuccess ? P2M_OK
                                                                                                                 : P2M_ERR_HIP;
 }
 #endif
