@@ -92,7 +92,39 @@ __device__ __forceinline__ void rows_weights_fill(const GemmArgs& g, int* rowtab
   if ((t & 63) == 0) wtab[BM + (t >> 6)] = s;
 }
 
-// per-tile BatchNorm partials (sum, centred M2).  `red` is block LDS that is free once the k loop is over.
+// The four tile rows of group gi (accumulator i = gi >> 2, registers 4 * (gi & 3) .. + 3) of a lane: ml0 + 0 .. 3.  ROWS: the
+// actual rows come from the row table in one 16-byte LDS read (ml0 is a multiple of four), -1 = no row; flat: m0 + ml0 + e.
+template <bool ROWS>
+__device__ __forceinline__ void epi_group_rows(const int* rowtab, long m0, long M, int ml0, int (&rl)[4]) {
+  if (ROWS) {
+    const u32x4 rt = *reinterpret_cast<const u32x4*>(rowtab + ml0);
+#pragma unroll
+    for (int e = 0; e < 4; e++) rl[e] = (int)rt[e];
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; e++) rl[e] = (m0 + ml0 + e < M) ? ml0 + e : -1;
+  }
+}
+
+// per-tile BatchNorm partials (sum, centred M2).  `smem` is block LDS that is free once the k loop is over.
+//
+// The store path (round 8).  A lane's 32 rows are walked in eight groups of four consecutive tile rows; inside a group the
+// columns (j) are the inner loop, so a group's row indices and row weights are read once (one ds_read_b128 each) and serve
+// every column.  The walk does not wait for memory with a store in front of it (as compiled: but for the last addend element
+// of a lane, and for the spilled values of the statistics walks of the 128-register row-set forms):
+//   * the output plane of a wave's 32 columns is chosen among the three kernel-argument pointers by scalar compares and
+//     selects (g.C[q] with a per-lane q was a vector load from the argument block and a vmcnt(0) per accumulator tile - on
+//     gfx9 that wait also drains every store issued before it);
+//   * the addend of group gi + 1 is requested BEFORE the stores of group gi are issued, unconditionally (rows and columns
+//     that do not exist read the block's first row / column 0 and the value is dropped by a select: a load under a
+//     per-lane condition is a branch and a full wait per element), and `has addend` is hoisted around the whole walk.  The
+//     wait for a group's addend is a counted vmcnt that leaves the stores of the group before it in flight;
+//   * the amax word is committed after the statistics, so no block barrier waits for a lane's store drain.
+// Per accumulator the value chain is unchanged (ldexp, + bias, fma act, max, + addend), each lane's csum[j] / m2[j] are
+// accumulated over i then r ascending as before, and the merges keep their operand order: results are bitwise the same.
+// Statistics: sums and M2 meet in two disjoint reduction buffers, two block barriers.  A wave whose columns all lie beyond N
+// (the upper half of a 64-wide tile at N = 32) skips every element loop and only attends the barriers.
+constexpr int EPI_BARRIERS = 2;     // block barriers of the statistics reduction (the staging waves of _ws attend them)
 template <int BN, bool EXTRA, bool ROWS>
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, floatx16 (&acc)[2][BN / 64], float* smem,
                                               const int* rowtab, int mt, long m0, int n0, int rs_i0, int wm, int wn,
@@ -100,113 +132,241 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, floatx16 (&acc)
   constexpr int WTN = BN / 2;
   constexpr int TN = WTN / 32;
   constexpr int TM = 2;
+  constexpr int NG = TM * 4;           // row groups per lane
   // C/D layout of 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
-  float bias_v[TN], sc_v[TN], sh_v[TN];
-  int ncol[TN];
-#pragma unroll
-  for (int j = 0; j < TN; j++) {
-    ncol[j] = n0 + wn * WTN + j * 32 + l31;
-    bias_v[j] = (g.bias != nullptr && ncol[j] < g.N) ? g.bias[ncol[j]] : 0.f;
-    sc_v[j] = (g.act_scale != nullptr && ncol[j] < g.N) ? g.act_scale[ncol[j]] : 1.f;
-    sh_v[j] = (g.act_scale != nullptr && ncol[j] < g.N) ? g.act_shift[ncol[j]] : 0.f;
-  }
-  float csum[TN];
-  float vmax = 0.f;
+  const int wnu = __builtin_amdgcn_readfirstlane(wn);                      // (wave-uniform, and known to be)
+  const bool live = n0 + wnu * WTN < g.N;                                  // wave-uniform
   const bool wst = ROWS && g.row_w != nullptr && g.stats != nullptr;      // weighted partials (block-uniform)
   const float* wtab = reinterpret_cast<const float*>(rowtab + BM);
+  const int mlw = wm * 64 + 4 * lhi;   // first tile row of the lane; group gi adds (gi >> 2) * 32 + (gi & 3) * 8
+  float csum[TN];
+  float vmax = 0.f;
 #pragma unroll
   for (int j = 0; j < TN; j++) csum[j] = 0.f;
+  // the 64 values of the lane one by one from here on: written back into the 16-register accumulator tuples, every element
+  // assembles a second copy of its tuple (two tiles in flight: 32 registers the row-set forms at 128 do not have)
+  float val[TM][TN][16];
 #pragma unroll
   for (int i = 0; i < TM; i++)
 #pragma unroll
+    for (int j = 0; j < TN; j++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) val[i][j][r] = acc[i][j][r];
+
+  if (live) {
+    // Addresses = wave-uniform 64-bit base (output plane + first row of the block's sample / tile: SALU) + a 32-bit byte
+    // offset per lane (row inside the sample / tile times the row pitch, + column): the stores and the addend loads take the
+    // `global_store v_off, v, s[base]` form, no 64-bit vector address per element (16 registers a group otherwise).
+    float bias_v[TN], sc_v[TN], sh_v[TN];
+    bool cok[TN];
+    unsigned c4[TN];                   // byte offset of the column inside its output plane
+    char* Cb[TN];                      // uniform: output plane of the wave's 32 columns, at the block's first row
+    const bool pair = EXTRA && !ROWS && g.pair_out;
+    const long rowbase = ROWS ? (long)(mt / g.tps) * g.V : m0;            // uniform: the rows of this block start here
+    const int rowbase32 = (int)rowbase;                                   // (ROWS: the row table holds ints)
+    const unsigned pitch = (unsigned)g.Nc * 4u;
+#pragma unroll
     for (int j = 0; j < TN; j++) {
-      const int n = ncol[j];
-      const int q = n / g.Nc;
-      const int c = n - q * g.Nc;
-      float* Cq = (n < g.N) ? g.C[q] : nullptr;
+      const int nu = n0 + wnu * WTN + j * 32;                              // uniform: first of the wave's 32 columns
+      const int n = nu + l31;
+      cok[j] = n < g.N;
+      bias_v[j] = (g.bias != nullptr && cok[j]) ? g.bias[n] : 0.f;
+      sc_v[j] = (g.act_scale != nullptr && cok[j]) ? g.act_scale[n] : 1.f;
+      sh_v[j] = (g.act_scale != nullptr && cok[j]) ? g.act_shift[n] : 0.f;
+      // the plane is n / Nc (n < N <= 3 Nc) without the division and without the per-lane read of the argument block.  The
+      // 32 columns of an MFMA tile lie in ONE plane: the MFMA entries admit Nc % 32 == 0 only (any other Nc runs k_naive_*)
+      const int q = (nu >= g.Nc ? 1 : 0) + (nu >= 2 * g.Nc ? 1 : 0);
+      float* const Cq = q == 0 ? g.C[0] : (q == 1 ? g.C[1] : g.C[2]);
+      Cb[j] = reinterpret_cast<char*>(Cq + (pair ? rowbase >> 1 : rowbase) * g.Nc);
+      c4[j] = (unsigned)(n - q * g.Nc) * 4u;
+    }
+    const char* const Ab = reinterpret_cast<const char*>(g.addend + (EXTRA && g.addend != nullptr ? rowbase * g.Nc : 0));
+    constexpr unsigned NOROW = 0xFFFFFFFFu;                                // (no byte offset of a row: those are multiples of 4)
+
+    // byte offsets of the four rows of group gi from the block's first row, or NOROW
+    auto row_offsets = [&](int gi, unsigned (&ro)[4]) {
+      int rl[4];
+      epi_group_rows<ROWS>(rowtab, m0, g.M, mlw + (gi >> 2) * 32 + (gi & 3) * 8, rl);
 #pragma unroll
-      for (int r = 0; r < 16; r++) {
-        const int ml = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
-        long row = ROWS ? (long)rowtab[ml] : m0 + ml;
-        const bool rok = ROWS ? (row >= 0) : (row < g.M);
-        float v = __builtin_ldexpf(acc[i][j][r], descale) + bias_v[j];     // descale: exact (two-fp16-slice mode), else 0
-        if (g.act_scale != nullptr) v = fmaf(v, sc_v[j], sh_v[j]);
-        if (g.act_relu) v = fmaxf(v, 0.f);
-        if (EXTRA && g.addend != nullptr && rok && Cq != nullptr) v += g.addend[row * g.N + n];
-        acc[i][j][r] = rok ? v : 0.f;
-        if (!(EXTRA && g.pair_out) && rok && Cq != nullptr) {
-#ifdef P2M_PL_ABL_NOSTORE
-          if (v == 12345.678f)
-#endif
-          Cq[row * g.Nc + c] = v;
-          csum[j] += wst ? wtab[ml] * v : v;
-          vmax = fmaxf(vmax, amax_abs(v));
-        }
-        // (round 6) the row addresses of four accumulator registers at a time: left alone, the scheduler forms all 64 store
-        // addresses first - 150-170 registers for a kernel whose k loop needs 112, i.e. one block per CU instead of two
-        if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+      for (int e = 0; e < 4; e++) {
+        ro[e] = rl[e] >= 0 ? (unsigned)(ROWS ? rl[e] - rowbase32 : rl[e]) * pitch : NOROW;
+        // (opaque from here on: knowing where `no row` comes from, the compiler threads the whole element - value chain, select,
+        // sums - into a branch per row, and the waits it then places at the joins are full ones)
+        asm volatile("" : "+v"(ro[e]));
       }
-      if (EXTRA && g.pair_out && Cq != nullptr) {   // rows (r, r+1), r even: the two children of one coarse vertex
+    };
+    // ADD: there is an addend.  KEEP: there are statistics - the values stay for the M2 pass and the sums are formed; without
+    // them a value is dead once it is stored (`has statistics` hoisted like `has addend`: the 64 kept values are what the
+    // row-set forms at 128 registers have no room for next to the addend in flight)
+    auto walk = [&](auto add_tag, auto keep_tag) {
+      constexpr bool ADD = decltype(add_tag)::value;
+      constexpr bool KEEP = decltype(keep_tag)::value;
+      float ad[2][ADD ? TN : 1][4];    // [parity of the group]
+      auto fetch = [&](int gi) {       // single output plane: N == Nc, the addend's offsets are the store's
+        unsigned ro[4];                // (read again when the group is stored: eight registers less across the walk)
+        row_offsets(gi, ro);
 #pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          long row = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
-          if (row < g.M) {
-            const float pv = acc[i][j][r] + acc[i][j][r + 1];
-            Cq[(row >> 1) * g.Nc + c] = pv;
-            vmax = fmaxf(vmax, amax_abs(pv));
+        for (int e = 0; e < 4; e++) {
+          const unsigned lo = ro[e] != NOROW ? ro[e] : 0u;
+#pragma unroll
+          for (int j = 0; j < TN; j++)
+            ad[gi & 1][j][e] = *reinterpret_cast<const float*>(Ab + (lo + (cok[j] ? c4[j] : 0u)));
+        }
+      };
+      if constexpr (ADD) fetch(0);
+      // the per-column constants have arrived before the first store is issued (one counted wait, here)
+#pragma unroll
+      for (int j = 0; j < TN; j++) asm volatile("" : "+v"(bias_v[j]), "+v"(sc_v[j]), "+v"(sh_v[j]));
+#pragma unroll
+      for (int gi = 0; gi < NG; gi++) {
+        const int i = gi >> 2, r0 = (gi & 3) * 4;
+        const int ml0 = mlw + i * 32 + (gi & 3) * 8;
+        if constexpr (ADD) {
+          if (gi + 1 < NG) fetch(gi + 1);
+        }
+        // the next group's requests stand before this group's stores; (round 6) and the row addresses of four accumulator
+        // registers at a time: left alone, the scheduler forms all 64 store addresses first - 150-170 registers for a kernel
+        // whose k loop needs 112, i.e. one block per CU instead of two
+        __builtin_amdgcn_sched_barrier(0);
+        unsigned ro[4];
+        row_offsets(gi, ro);
+        float vg[TN][4];               // the group's values
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+          const int r = r0 + e;
+          const bool rok = ro[e] != NOROW;
+#pragma unroll
+          for (int j = 0; j < TN; j++) {
+            float v = __builtin_ldexpf(val[i][j][r], descale) + bias_v[j];     // descale: exact (two-fp16-slice mode), else 0
+            if (g.act_scale != nullptr) v = fmaf(v, sc_v[j], sh_v[j]);
+            if (g.act_relu) v = fmaxf(v, 0.f);
+            if constexpr (ADD) v += ad[gi & 1][j][e];    // (what a row or column that does not exist gets is dropped below)
+            // the value is formed (and kept) for every lane - what a row that does not exist keeps is never used: the sums,
+            // the pair sums and the M2 pass all ask for the row - and only the store stands under the lane's condition:
+            // sunk into that branch, what is kept is a copy of its whole tile on either side of it
+            asm volatile("" : "+v"(v));
+            vg[j][e] = v;
+            if constexpr (KEEP) val[i][j][r] = v;
+            if (!pair && rok && cok[j]) {
+#ifdef P2M_PL_ABL_NOSTORE
+              if (v == 12345.678f)
+#endif
+              *reinterpret_cast<float*>(Cb[j] + (ro[e] + c4[j])) = v;
+            }
           }
         }
+        if (pair) {   // rows (r, r+1), r even: the two children of one coarse vertex
+#pragma unroll
+          for (int e = 0; e < 4; e += 2) {
+            if (m0 + ml0 + e < g.M) {
+#pragma unroll
+              for (int j = 0; j < TN; j++)
+                if (cok[j]) {
+                  const float pv = vg[j][e] + (m0 + ml0 + e + 1 < g.M ? vg[j][e + 1] : 0.f);
+                  *reinterpret_cast<float*>(Cb[j] + ((unsigned)((ml0 + e) >> 1) * pitch + c4[j])) = pv;
+                  vmax = fmaxf(vmax, amax_abs(pv));
+                }
+            }
+          }
+        } else {
+          // sums and maximum of the group, from the values just kept (an element that does not exist adds + 0 and max(., 0):
+          // csum and vmax are never -0, they stay as they were); the weights are read when the addend's registers are free
+          f32x4 w4 = {0.f, 0.f, 0.f, 0.f};
+          if (KEEP && wst) w4 = *reinterpret_cast<const f32x4*>(wtab + ml0);
+#pragma unroll
+          for (int e = 0; e < 4; e++)
+#pragma unroll
+            for (int j = 0; j < TN; j++) {
+              const float v = vg[j][e];
+              const bool ok = ro[e] != NOROW && cok[j];
+              if constexpr (KEEP) {
+                const float term = wst ? w4[e] * v : v;
+                csum[j] += ok ? term : 0.f;
+              }
+              vmax = fmaxf(vmax, ok ? amax_abs(v) : 0.f);
+            }
+        }
+        // formed HERE: left to the compiler the sums and the maximum sink behind the whole walk, with every weight and lane
+        // condition of the 64 elements kept until then (254 registers)
+#pragma unroll
+        for (int j = 0; j < TN; j++) asm volatile("" : "+v"(csum[j]));
+        asm volatile("" : "+v"(vmax));
+        __builtin_amdgcn_sched_barrier(0);
       }
+    };
+    const bool add = EXTRA && g.addend != nullptr;
+    if (g.stats != nullptr) {
+      if (add) walk(std::true_type{}, std::true_type{});
+      else walk(std::false_type{}, std::true_type{});
+    } else {
+      if (add) walk(std::true_type{}, std::false_type{});
+      else walk(std::false_type{}, std::false_type{});
     }
-  if (g.amax_out != nullptr) amax_commit(g.amax_out, vmax);
-  if (g.stats == nullptr) return;
+  }
 
-  // column sums over the 128-row tile: lane^32 holds the same column, the other wm wave the other 64 rows
-  float* red = smem;  // [2 (wm)][BN]   (safe: all waves passed the last __syncthreads of the k loop)
-  long rows_valid = ROWS ? (long)(g.nset - rs_i0) : g.M - m0;
-  if (rows_valid > BM) rows_valid = BM;
+  if (g.stats != nullptr) {
+    // column sums over the 128-row tile: lane^32 holds the same column, the other wm wave the other 64 rows
+    float* red = smem;             // [2 (wm)][BN] sums      (safe: all waves passed the last __syncthreads of the k loop)
+    float* red2 = smem + 2 * BN;   // [2 (wm)][BN] M2
+    long rows_valid = ROWS ? (long)(g.nset - rs_i0) : g.M - m0;
+    if (rows_valid > BM) rows_valid = BM;
+    if (live) {
 #pragma unroll
-  for (int j = 0; j < TN; j++) {
-    csum[j] += __shfl_xor(csum[j], 32);
-    if (lhi == 0) red[wm * BN + wn * WTN + j * 32 + l31] = csum[j];
-  }
-  __syncthreads();
-  float cm2[TN];
-#pragma unroll
-  for (int j = 0; j < TN; j++) {
-    const int cl = wn * WTN + j * 32 + l31;
-    const float tot = red[cl] + red[BN + cl];
-    const float mean = tot / (wst ? wtab[BM] + wtab[BM + 1] : (float)rows_valid);
-    float m2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < TM; i++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) {
-        const int ml = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
-        float d = acc[i][j][r] - mean;
-        if (ROWS ? (rowtab[ml] >= 0) : (m0 + ml < g.M)) m2 += wst ? wtab[ml] * d * d : d * d;
+      for (int j = 0; j < TN; j++) {
+        csum[j] += __shfl_xor(csum[j], 32);
+        if (lhi == 0) red[wm * BN + wn * WTN + j * 32 + l31] = csum[j];
       }
-    m2 += __shfl_xor(m2, 32);
-    cm2[j] = m2;
-    csum[j] = tot;
-  }
-  __syncthreads();
+    }
+    __syncthreads();
+    if (live) {
+      float mean[TN], m2[TN];
 #pragma unroll
-  for (int j = 0; j < TN; j++)
-    if (lhi == 0) red[wm * BN + wn * WTN + j * 32 + l31] = cm2[j];
-  __syncthreads();
-  if (wm == 0 && lhi == 0) {
+      for (int j = 0; j < TN; j++) {
+        const int cl = wn * WTN + j * 32 + l31;
+        const float tot = red[cl] + red[BN + cl];
+        mean[j] = tot / (wst ? wtab[BM] + wtab[BM + 1] : (float)rows_valid);
+        m2[j] = 0.f;
+        csum[j] = tot;
+      }
 #pragma unroll
-    for (int j = 0; j < TN; j++) {
-      const int cl = wn * WTN + j * 32 + l31;
-      const int n = n0 + cl;
-      if (n < g.N) {
-        float* st = g.stats + (long)mt * 2 * g.N;
-        st[n] = csum[j];
-        st[g.N + n] = red[cl] + red[BN + cl];
+      for (int gi = 0; gi < NG; gi++) {
+        const int i = gi >> 2, r0 = (gi & 3) * 4;
+        const int ml0 = mlw + i * 32 + (gi & 3) * 8;
+        int rl[4];
+        epi_group_rows<ROWS>(rowtab, m0, g.M, ml0, rl);
+        f32x4 w4 = {0.f, 0.f, 0.f, 0.f};
+        if (wst) w4 = *reinterpret_cast<const f32x4*>(wtab + ml0);
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+#pragma unroll
+          for (int j = 0; j < TN; j++) {
+            // (w d) d + m2 with the last product fused, as this sum has always been compiled; written out so that it stays so
+            const float d = val[i][j][r0 + e] - mean[j];
+            const float wd = wst ? w4[e] * d : d;
+            m2[j] = rl[e] >= 0 ? fmaf(wd, d, m2[j]) : m2[j];
+          }
+      }
+#pragma unroll
+      for (int j = 0; j < TN; j++) {
+        m2[j] += __shfl_xor(m2[j], 32);
+        if (lhi == 0) red2[wm * BN + wn * WTN + j * 32 + l31] = m2[j];
+      }
+    }
+    __syncthreads();
+    if (live && wm == 0 && lhi == 0) {
+#pragma unroll
+      for (int j = 0; j < TN; j++) {
+        const int cl = wn * WTN + j * 32 + l31;
+        const int n = n0 + cl;
+        if (n < g.N) {
+          float* st = g.stats + (long)mt * 2 * g.N;
+          st[n] = csum[j];
+          st[g.N + n] = red2[cl] + red2[BN + cl];
+        }
       }
     }
   }
+  if (g.amax_out != nullptr) amax_commit(g.amax_out, vmax);
 }
 
 // KB = K chunk staged per barrier (16: 34 KB LDS -> 3 blocks/CU; 32: 67 KB -> 2 blocks/CU);
@@ -221,7 +381,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_planes(GemmArgs g) {
   constexpr int AROWS = 256 / (KB / 4);           // rows of A covered per pass
   constexpr int BPASS = KB * BN / 4 / 256;        // float4 B loads per thread per chunk
   constexpr int BROWS = 256 / (BN / 4);           // rows of B covered per pass
-  __shared__ float smem[2 * BM * LDA + 2 * KB * BN + (ROWS ? ROWTAB_WORDS : 0)];
+  __shared__ __attribute__((aligned(16))) float smem[2 * BM * LDA + 2 * KB * BN + (ROWS ? ROWTAB_WORDS : 0)];   // (16: the epilogue reads the row table four rows at a time)
   float* As = smem;
   float* Bs = smem + 2 * BM * LDA;
   int* rowtab = reinterpret_cast<int*>(smem + 2 * BM * LDA + 2 * KB * BN);   // ROWS: actual row of each tile row, -1 = none
@@ -622,10 +782,9 @@ __global__ __launch_bounds__(512, (BN == 128 && ROWS) ? 4 : 2) void k_gemm_plane
   if (!producer) {
     gemm_epilogue<BN, EXTRA, ROWS>(g, acc, smem, rowtab, mt, m0, n0, rs_i0, wm, wn, l31, lhi, descale);
   } else {
-    if (g.stats != nullptr) {                   // the three block barriers of the statistics reduction
-      __syncthreads();
-      __syncthreads();
-      __syncthreads();
+    if (g.stats != nullptr) {                   // the block barriers of the statistics reduction
+#pragma unroll
+      for (int b = 0; b < EPI_BARRIERS; b++) __syncthreads();
     }
   }
 }
@@ -673,7 +832,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_rows_k1(GemmArgs g) {
   constexpr int KSTEPS = KP / 16;         // MFMA k steps per pass (2 or 4: the B double buffer's parity is static)
   constexpr int A_IMG = NS * BM * LDX;    // bf16 / fp16 elements
   static_assert(KP == 64 || KP == 32, "pass width");
-  static_assert(A_IMG / 2 >= 2 * BN, "the epilogue's reduction buffer lives in the image");
+  static_assert(A_IMG / 2 >= 4 * BN, "the epilogue's two reduction buffers live in the image");
   __shared__ __attribute__((aligned(16))) float smem[A_IMG / 2 + ROWTAB_WORDS];
   __shared__ __attribute__((aligned(16))) float actco[2 * 256];
   unsigned short* As = reinterpret_cast<unsigned short*>(smem);
@@ -1545,16 +1704,27 @@ __global__ __launch_bounds__(512, 2) void k_gemm_tn_ws(TnArgs g) {
         const int n = n0 + wn * WTN + j * 32 + l31;
         // accumulate form (p2m_gemm_tn_acc): the 16 old values of the tile first, all loads in flight, then add and store
         // (one load - add - store chain per element waited for every load in turn: 116 us for a 4096 x 4096 gradient)
-        float old[16];
+        // (round 8) `accumulate` is hoisted around the tile: under a per-element condition the loads were branches whose
+        // vmcnt(0) stood in the plain form too, where it drained the 16 stores of the tile before - the form every conv's
+        // weight gradient runs.  The plain form keeps its `+ 0`: -0 is stored as +0, as before.
+        if (g.accum) {
+          float old[16];
 #pragma unroll
-        for (int r = 0; r < 16; r++) {
-          const int krow = kk0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
-          old[r] = (g.accum && krow < g.Ktot && n < g.N) ? Pc[(long)krow * g.N + n] : 0.f;
-        }
+          for (int r = 0; r < 16; r++) {
+            const int krow = kk0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+            old[r] = (krow < g.Ktot && n < g.N) ? Pc[(long)krow * g.N + n] : 0.f;
+          }
 #pragma unroll
-        for (int r = 0; r < 16; r++) {
-          const int krow = kk0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
-          if (krow < g.Ktot && n < g.N) Pc[(long)krow * g.N + n] = __builtin_ldexpf(acc[i][j][r], descale) + old[r];
+          for (int r = 0; r < 16; r++) {
+            const int krow = kk0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+            if (krow < g.Ktot && n < g.N) Pc[(long)krow * g.N + n] = __builtin_ldexpf(acc[i][j][r], descale) + old[r];
+          }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 16; r++) {
+            const int krow = kk0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+            if (krow < g.Ktot && n < g.N) Pc[(long)krow * g.N + n] = __builtin_ldexpf(acc[i][j][r], descale) + 0.f;
+          }
         }
       }
   }
@@ -2071,6 +2241,8 @@ extern "C" int p2m_gemm_planes_rows(p2m_graph_t gh, int32_t row_set, int32_t B, 
   const Graph& gr = *reinterpret_cast<const Graph*>(gh);
   const RowSet rs = row_set_of(gr, row_set);
   if (B <= 0 || rs.n == 0) return P2M_OK;
+  // the epilogue addresses C and the addend as sample base + a 32-bit byte offset (as the k loop does A)
+  P2M_CHECK_ARG((long)rs.V * N < (1l << 30), "one sample of C must stay below 4 GiB (V * N < 2^30)");
   GemmArgs g;
   g.A[0] = A0; g.A[1] = A1; g.A[2] = A2;
   for (int p = 0; p < nplanesA; p++) P2M_CHECK_ARG(g.A[p] != nullptr, "missing A plane");
