@@ -97,8 +97,8 @@ def regressor(J, nv, seed):
 
 def chain_case(B, nv, seed, joint_set="coco", rot=None, flip=None):
     """A seeded batch for the chain: a person-sized point cloud 3 - 6 m in front of a 1000 - 1500 px camera.  joint_set
-    'coco': 17 regressed joints + pelvis + neck, root = pelvis (index 17); 'human36': the input set is the reg set.
-    nv = 1 makes every joint coincide: the degenerate bbox."""
+    'coco': 17 regressed joints + pelvis + neck, root = pelvis (index 17); 'human36': the input set is the reg set;
+    'cap32': the tables at the kernel's caps (cap32_case).  nv = 1 makes every joint coincide: the degenerate bbox."""
     rng = np.random.default_rng(seed)
     verts = (rng.normal(0, 1, (B, nv, 3)) * [0.25, 0.5, 0.15]).astype(np.float32)
     trans = np.stack([rng.uniform(-0.4, 0.4, B), rng.uniform(-0.4, 0.4, B), rng.uniform(3, 6, B)], axis=1).astype(np.float32)
@@ -108,6 +108,9 @@ def chain_case(B, nv, seed, joint_set="coco", rot=None, flip=None):
              mesh_scale=1000.0, W=W, H=H, joint_set=joint_set)
     if joint_set == "coco":
         c.update(in_R=regressor(17, nv, seed + 2), midpoints=COCO_MIDPOINTS, input_root=17, flip_pairs=COCO_FLIP_PAIRS)
+    elif joint_set == "cap32":
+        c.update(reg_R=cap_regressor(32, nv, seed + 1), reg_root=31, in_R=cap_regressor(28, nv, seed + 2),
+                 midpoints=CAP32_MIDPOINTS, input_root=31, flip_pairs=CAP32_FLIP_PAIRS)
     else:
         c.update(in_R=None, midpoints=(), input_root=0, flip_pairs=H36M_FLIP_PAIRS)
     c["rot"] = rng.choice([0.0, 17.5, -60.0, 90.0, 33.25], B).astype(np.float32) if rot is None else np.asarray(rot, np.float32)
@@ -153,3 +156,185 @@ def table(J, seed):
     weight[0] = 0.0
     weight[J - 1] = 1.0                      # J = 1: the one joint always gets its error, so values are compared
     return mean, std, weight
+
+
+# ---- the edges of the chain (test_sample_edges_cpu.py, test_gpu_sample_edges.py) -------------------------------------------
+def mesh_arm(verts_ptr, mesh_ptr, b, nv):
+    """Which arm of k_sample_main's mesh stream sample b takes, from the integer addresses of verts and mesh (csrc/sample.hip,
+    'the mesh'): (vec, head, n4, tail).  vec: the sample's input and output have the same offset inside a 16-byte line; then
+    a scalar head up to the next line, n4 float4 steps and a scalar tail.  The scalar arm is one loop: (False, n, 0, 0)."""
+    n = 3 * nv
+    vb, mo = int(verts_ptr) + 4 * b * n, int(mesh_ptr) + 4 * b * n
+    if ((vb ^ mo) & 15) != 0:
+        return False, n, 0, 0
+    head = min(n, ((16 - (vb & 15)) & 15) >> 2)
+    n4 = (n - head) >> 2
+    return True, head, n4, n - head - 4 * n4
+
+
+MESH_B = 5
+MESH_NV = (1, 2, 4, 7, 63, 345)              # n % 4 = 3, 2, 0, 1, 1, 3; n <= head; n4 = 0 with a tail; n4 > 256
+MESH_ALL_PAIRS_NV = (7, 63)
+MESH_PAD = 4                                 # sentinel floats in front of a view at offset 0 (a whole 16-byte line)
+MESH_SPLITS = ((9,), (1, 8), (3, 6))         # plain buffers, nv = 63: a batch of 9, whole and in parts
+
+
+def mesh_pairs(nv):
+    """The (k_in, k_out) float offsets of the verts and mesh views of one vertex count: all 16 for nv in {7, 63}, the four
+    equal pairs (the vec arm at every head) and one unequal pair (the scalar arm) for the others."""
+    if nv in MESH_ALL_PAIRS_NV:
+        return [(i, o) for i in range(4) for o in range(4)]
+    return [(k, k) for k in range(4)] + [(nv % 4, (nv + 2) % 4)]
+
+
+def mesh_flat_len(B, nv):
+    """Floats of the flat tensor a view of offset k in 0..3 sits in, as flat[MESH_PAD + k : MESH_PAD + k + 3 B nv]: at least
+    4 floats in front and 5 behind."""
+    return 2 * MESH_PAD + 4 + 3 * B * nv
+
+
+def mesh_case(nv):
+    """The coco set on nv vertices.  The bars are the fp32 error class of a 257-vertex cloud, whose joint box is person-sized
+    (60 x 100 px at least); a handful of random vertices can span a box barely over the 1 px that keeps a sample alive,
+    and pose2d = (p - mean) / std is then ill-conditioned in any fp32 evaluation (the restatement's own fp32 run was 11 x its
+    class on such a 2-vertex case).  For nv in 2..7 the first two vertices are therefore put on opposite corners of a
+    person-sized box; test_sample_edges_cpu.py holds every case's own fp32 restatement error to half the bar."""
+    c = chain_case(MESH_B, nv, 300 + nv, "coco")
+    if 1 < nv <= 7:
+        c["verts"][:, 0, :2] = np.float32([-0.25, -0.5])
+        c["verts"][:, 1, :2] = np.float32([0.25, 0.5])
+    return c
+
+
+def mesh_split_case():
+    return chain_case(9, 63, 97, "coco")
+
+
+def mesh_table(base_in=0, base_out=0):
+    """Every (case, sample) of the mesh-arm tests with its predicted arm: rows (nv, k_in, k_out, b, vec, head, n4, tail).  The
+    views' addresses are base + 4 (MESH_PAD + k); the plain buffers of the batch splits are fresh allocations (k = 0).  The
+    defaults take every allocation to start on a 16-byte line; the GPU tests recompute each row from data_ptr()."""
+    rows = []
+    for nv in MESH_NV:
+        for k_in, k_out in mesh_pairs(nv):
+            for b in range(MESH_B):
+                rows.append((nv, k_in, k_out, b) + mesh_arm(base_in + 4 * (MESH_PAD + k_in), base_out + 4 * (MESH_PAD + k_out), b, nv))
+    for parts in MESH_SPLITS:
+        for B in parts:
+            rows += [(63, 0, 0, b) + mesh_arm(base_in, base_out, b, 63) for b in range(B)]
+    return rows
+
+
+def check_mesh_coverage(arms):
+    """arms: (nv, vec, head, n4, tail) per (case, sample).  The vec arm with every head and every tail in 0..3, its sub-cases
+    n <= head, n4 == 0 with elements left, and n4 > 256 (a thread takes two float4 steps), the scalar arm, and at least half
+    of all pairs on the vec arm.  Returns the share on the vec arm."""
+    arms = list(arms)
+    vec = [a for a in arms if a[1]]
+    assert {a[2] for a in vec} == {0, 1, 2, 3}, "vec arm: a head in 0..3 is missing"
+    assert {a[4] for a in vec} == {0, 1, 2, 3}, "vec arm: a tail in 0..3 is missing"
+    assert any(3 * a[0] <= a[2] and a[2] > 0 for a in vec), "vec arm: no sample with n <= head"
+    assert any(a[3] == 0 and 3 * a[0] - a[2] > 0 for a in vec), "vec arm: no sample with n4 == 0 < n - head"
+    assert any(a[3] > 256 for a in vec), "vec arm: no sample with n4 > 256"
+    assert len(vec) < len(arms), "the scalar arm is not reached"
+    assert 2 * len(vec) >= len(arms), f"only {len(vec)} of {len(arms)} (case, sample) pairs are on the vec arm"
+    return len(vec) / len(arms)
+
+
+CAP32_MIDPOINTS = ((11, 12), (5, 6), (0, 1), (26, 27))        # joints 28 .. 31 of the input set
+CAP32_FLIP_PAIRS = tuple((i, 31 - i) for i in range(16))      # 16 disjoint pairs over all 32 joints; (0, 31) holds joint 31
+CAP_ROW_ENTRIES = (1, 6, 64, 65, -1)                          # rows 0 .. 4 (-1: dense); the CSR loop's pass edges
+
+
+def cap_regressor(J, nv, seed):
+    """Row-stochastic regressor whose first rows have 1, 6, 64, 65 and nv (dense) entries - one lane, a partial pass, one full
+    pass of the 64 lanes, a second pass of one lane, several passes with a partial last one - and the rest 6; every stored
+    weight is positive, so the CSR rows have exactly these lengths."""
+    rng = np.random.default_rng(seed)
+    R = np.zeros((J, nv), np.float32)
+    for j in range(J):
+        k = CAP_ROW_ENTRIES[j] if j < min(J, len(CAP_ROW_ENTRIES)) else 6
+        k = nv if k < 0 else min(k, nv)
+        w = rng.uniform(0.1, 1.0, k).astype(np.float32)
+        R[j, rng.choice(nv, size=k, replace=False)] = w / w.sum()
+    return R
+
+
+def cap32_case(B, seed=50):
+    """The joint set at the kernel's caps: Jr = 32, Ji = 28 + 4 midpoints = 32, 16 flip pairs, both roots joint 31 (of the
+    input set a midpoint), nv = 257."""
+    return chain_case(B, 257, seed, "cap32")
+
+
+CAP32_NOISE_B = 9
+
+
+def cap32_noise_case():
+    """Table noise at J = 32 with drawn rot / flip: (case, keyword arguments of sample_ref.chain).  65 samples for the
+    restatement's error class; the GPU runs the first CAP32_NOISE_B of them (a sample depends on its global index alone)."""
+    c = cap32_case(65, 83)
+    kw = dict(rot=None, flip=None, rot_factor=30.0, flip_enabled=True, noise=2, seed=779, first_index=(1 << 33) + 11,
+              table=table(32, seed=13))
+    return c, kw
+
+
+def tiny_set_case():
+    """Jr = 1 and Ji = 2 without midpoints: the smallest joint tables (B = 4, nv = 63).  The box of two joints must be more
+    than 1 px wide and high to be live - a condition on the regressor's seed (here at least 25 px; test_sample_edges_cpu)."""
+    c = chain_case(4, 63, 44, "coco")
+    c.update(reg_R=regressor(1, 63, 45), reg_root=0, in_R=regressor(2, 63, 47), midpoints=(), input_root=1, flip_pairs=((0, 1),))
+    return c
+
+
+def tiny_given(c):
+    """An 'annotated' reg joint [B, 1, 3] in mm for tiny_set_case: the regressed one moved by (7, -3, 11) mm.  With one joint
+    both sets equal their means, so the fit error is exactly 0 whatever the offset."""
+    mm = (c["verts"].astype(np.float64) + c["trans"][:, None]) * 1000.0
+    return (np.einsum("jv,svc->sjc", c["reg_R"].astype(np.float64), mm) + np.array([7.0, -3.0, 11.0])).astype(np.float32)
+
+
+def empty_row_case():
+    """The coco set with row 3 of the input regressor empty: that joint sits at the origin, z = 0 (B = 3, nv = 63)."""
+    c = chain_case(3, 63, 47, "coco")
+    c["in_R"][3] = 0
+    return c
+
+
+def option_case(variant=None):
+    """B = 4, nv = 63, coco set.  'trans_none': the translation is in the vertices and trans is None; 'mm': vertices and
+    translation in mm with mesh_scale = 1; 'rot_edges': rot = 180, 360, -0.0, 0.0."""
+    c = chain_case(4, 63, 48, "coco")
+    if variant == "trans_none":
+        c["verts"] = (c["verts"] + c["trans"][:, None]).astype(np.float32)
+        c["trans"] = None
+    elif variant == "mm":
+        c["verts"], c["trans"] = (c["verts"] * np.float32(1000)).astype(np.float32), (c["trans"] * np.float32(1000)).astype(np.float32)
+        c["mesh_scale"] = 1.0
+    elif variant == "rot_edges":
+        c["rot"] = np.array([180.0, 360.0, -0.0, 0.0], np.float32)
+    else:
+        assert variant is None, variant
+    return c
+
+
+OPTION_AUG = dict(seed=21, first=1234, rot_factor=30.0)       # the stream state of the half-drawn augmentation cases
+
+
+def head_of(c, n):
+    """The first n samples of a chain case."""
+    return {k: (v[:n] if k in ("verts", "trans", "focal", "princpt", "rot", "flip") and v is not None else v) for k, v in c.items()}
+
+
+def late_zero_case(base):
+    """human36 set, B = 3, given joints.  base: the restatement's run of late_zero_chain_case().  Returns given_cam, the sane
+    given_img and the one whose middle sample has x = +-3e38 on two joints: finite, so it passes the first kernel's checks,
+    but the fp32 box width overflows and the standardisation fails."""
+    gcam = (base["reg_pose3d"] + np.array([7.0, -3.0, 11.0])).astype(np.float32)
+    sane = (base["img"] + 3.0).astype(np.float32)
+    bad = sane.copy()
+    bad[1, 2, 0], bad[1, 5, 0] = 3e38, -3e38
+    return gcam, sane, bad
+
+
+def late_zero_chain_case():
+    return chain_case(3, 63, 49, "human36")
