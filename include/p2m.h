@@ -640,6 +640,36 @@ int p2m_body_forward(const float* pose, const float* pose_mean, const float* bet
                      const int32_t* xr_idx, const float* xr_val, int32_t n_extra, void* workspace, int64_t workspace_bytes,
                      float* verts, float* joints, float* extra, void* stream);
 
+/* ---- body-model layer: backward (csrc/body_bwd.hip) --------------------------------------------------------------------------
+ * Gradients of a scalar loss with respect to pose, betas and trans of ONE p2m_body_forward call, from its gradients with
+ * respect to verts, joints and extra.  The caller passes the inputs and tables of that call again and the forward workspace
+ * as that call left it (fwd_workspace: coefficient rows, skinning matrices, offsets; read only) - nothing else is kept
+ * between the two.  has_trans != 0: the forward was given trans (then center_joint is ignored, as there).
+ *   g_verts [B, V, 3], g_joints [B, n_joints_out, 3], g_extra [B, n_extra, 3]: contiguous, each may be NULL (no gradient
+ *   arrives through that output; no zeros are read), at least one is not.
+ *   g_pose [B, 3 J], g_betas [B, nb], g_trans [B, 3]: written (not accumulated); each may be NULL (not wanted, its work is
+ *   skipped), at least one is not.  g_betas needs betas_per_sample != 0, g_trans needs has_trans != 0.
+ *   dirs_t [3 V][Kp], Kp = nb + 9 (J - 1) rounded up to a multiple of 4: the direction table vertex-major (row g = entry g
+ *   of every coefficient, zero padded); needed for g_pose / g_betas, else it may be NULL.
+ *   xc_ptr [V + 1] / xc_idx / xc_val: the extra regressor by COLUMN (CSC: the entries of vertex v, joints ascending);
+ *   needed when g_extra is given.
+ *   workspace: p2m_body_backward_workspace(B, V, J, nb) bytes, 16-byte aligned: per-block partial sums
+ *   [ceil(V / 64)][B] x (12 (J + 1) doubles + Kp floats), written and read once.
+ * Two launches on `stream`; nothing allocates or synchronises.  No atomics: the vertex stage reduces each 64-vertex tile in a
+ * fixed order (float64 inside the tile for the skinning-matrix and offset sums), the pose stage folds the tiles in tile order
+ * and runs the chain and batch_rodrigues' derivative (its + 1e-8 included, no special case at a zero rotation) in float64.
+ * A sample's gradient is bitwise the same in any batch.  Limits and alignment as p2m_body_forward. */
+int64_t p2m_body_backward_workspace(int32_t B, int32_t V, int32_t J, int32_t nb);
+int p2m_body_backward(const float* pose, const float* pose_mean, const float* betas, int32_t betas_per_sample,
+                      int32_t has_trans, int32_t center_joint, float scale, int32_t B, int32_t V, int32_t J, int32_t nb,
+                      const float* v_template, const float* dirs, const float* dirs_t, const float* weights_t,
+                      const float* joint_template, const float* joint_shapedirs, const int32_t* parents,
+                      const int32_t* joint_slot, int32_t n_joints_out, const int32_t* tip_vert, const int32_t* tip_slot,
+                      int32_t n_tips, const int32_t* xc_ptr, const int32_t* xc_idx, const float* xc_val, int32_t n_extra,
+                      const void* fwd_workspace, int64_t fwd_workspace_bytes, const float* g_verts, const float* g_joints,
+                      const float* g_extra, void* workspace, int64_t workspace_bytes, float* g_pose, float* g_betas,
+                      float* g_trans, void* stream);
+
 /* ---- training-sample noise: synthetic 2D detector errors (csrc/sample.hip, csrc/p2m_philox.h) ---------------------------
  * Every released recipe of the reference trains on noisy 2D input (use_gt_input: False): the dataset replaces the clean
  * projected joints by synthetic detector errors on a dataloader worker (data/AMASS/dataset.py:311-330 and its siblings).

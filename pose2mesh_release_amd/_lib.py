@@ -124,6 +124,10 @@ HIP_SYMBOLS = {
     "p2m_body_workspace": (_i64, [_i32, _i32, _i32]),
     "p2m_body_forward": (_c.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _f32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "p2m_body_backward_workspace": (_i64, [_i32, _i32, _i32, _i32]),
+    "p2m_body_backward": (_c.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp,
+                                     _i64, _vp, _vp, _vp, _vp]),
     "p2m_pose_noise_coco": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "p2m_pose_noise_table": (_c.c_int, [_vp, _vp, _vp, _vp, _i32, _f32, _f32, _vp, _vp, _i32, _vp]),
     "p2m_train_sample_workspace": (_i64, [_i32]),

@@ -6,8 +6,12 @@ once per sample on a dataloader worker to make its target mesh (get_smpl_coord /
   BodyModel.from_layer(layer)                                                       from a constructed reference layer
   verts, joints[, extra] = model(pose, betas=None, trans=None)                      one p2m_body_forward call
 
-Forward only, fp32, on the current stream; the launch path allocates and synchronises nothing once the buffers of a batch
-size exist, so a call can sit in a captured graph.  There is no CPU fallback: CPU tensors raise.
+  layer = BodyLayer(model);  verts, joints[, extra] = layer(pose, betas, trans)      the same forward, differentiable
+
+BodyModel is forward only, fp32, on the current stream; the launch path allocates and synchronises nothing once the buffers
+of a batch size exist, so a call can sit in a captured graph.  BodyLayer is the opt-in differentiable entry: new output
+tensors per call and one p2m_body_backward call for the gradients of pose, betas and trans.  There is no CPU fallback: CPU
+tensors raise.
 """
 import ctypes as _ct
 
@@ -33,11 +37,11 @@ def _stream():
     return _ct.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _cuda_f32(x, name, shape):
+def _cuda_f32(x, name, shape, grad_ok=False):
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise _lib.P2MError(f"{name}: the body-model kernels need a CUDA tensor (there is no CPU path)")
-    if x.requires_grad:
-        raise _lib.P2MError(f"{name}: requires grad, and the body-model layer is forward only")
+    if x.requires_grad and not grad_ok:
+        raise _lib.P2MError(f"{name}: requires grad, and BodyModel is forward only (BodyLayer is the differentiable entry)")
     if tuple(x.shape) != shape:
         raise ValueError(f"{name}: expected {list(shape)}, got {list(x.shape)}")
     return x.contiguous() if x.dtype == torch.float32 else x.float().contiguous()
@@ -165,8 +169,14 @@ class BodyModel:
             host.update(xr_ptr=t["jr_ptr"], xr_idx=t["jr_idx"], xr_val=t["jr_val"])
             if t["jr_val"].size == 0:                                      # an all-zero regressor: keep the tables non-empty
                 host.update(xr_idx=_np.zeros(1, _np.int32), xr_val=_np.zeros(1, _np.float32))
+            # the same regressor by column, for the backward (BodyLayer): the entries of a vertex, joints ascending
+            self._host_grad = {"xc_ptr": t["vj_ptr"], "xc_idx": _np.concatenate([t["vj_idx"], _np.zeros(1, _np.int32)]),
+                               "xc_val": _np.concatenate([t["vj_val"], _np.zeros(1, _np.float32)])}
+        else:
+            self._host_grad = {}
         self._host = host
         self._dev = None
+        self._dev_grad = None
         self._bufs = {}
 
     @classmethod
@@ -196,6 +206,18 @@ class BodyModel:
             self._dev = (dev, {k: torch.from_numpy(_np.ascontiguousarray(v)).to(dev) for k, v in self._host.items()})
             self._bufs = {}
         return self._dev[1]
+
+    def _grad_tables(self, dev):
+        """What only the backward reads, uploaded on the first differentiable call: the direction table vertex-major
+        [3 V][K rounded up to 4] (the reference's own [V, 3, .] layout; SMPL: + 18 MB) and the extra regressor by column."""
+        if self._dev_grad is None or self._dev_grad[0] != dev:
+            d = self._host["dirs"]
+            dt = _np.zeros((d.shape[1], (d.shape[0] + 3) // 4 * 4), _np.float32)
+            dt[:, :d.shape[0]] = d.T
+            g = {k: torch.from_numpy(_np.ascontiguousarray(v)).to(dev) for k, v in self._host_grad.items()}
+            g["dirs_t"] = torch.from_numpy(dt).to(dev)
+            self._dev_grad = (dev, g)
+        return self._dev_grad[1]
 
     def _buffers(self, B, dev):
         b = self._bufs.get(B)
@@ -243,3 +265,97 @@ class BodyModel:
         if self.JX:
             return buf["verts"], buf["joints"], buf["extra"]
         return buf["verts"], buf["joints"]
+
+
+class _BodyFunction(torch.autograd.Function):
+    """One p2m_body_forward call into fresh tensors; the backward is one p2m_body_backward call.  The forward workspace
+    (coefficient rows, skinning matrices, offsets) and the inputs are saved per call."""
+
+    @staticmethod
+    def forward(ctx, model, pose, betas, trans):
+        B, dev = int(pose.shape[0]), pose.device
+        t = model._device_tables(dev)
+        nbytes = int(_lib.hip().p2m_body_workspace(B, model.J, model.nb))
+        if nbytes < 0:
+            raise _lib.P2MError("p2m_body_workspace: bad shape")
+        ws = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
+        verts = torch.empty((B, model.V, 3), device=dev, dtype=torch.float32)
+        joints = torch.empty((B, model.NJ, 3), device=dev, dtype=torch.float32)
+        extra = torch.empty((B, model.JX, 3), device=dev, dtype=torch.float32) if model.JX else None
+        with torch.cuda.device(dev):
+            _lib.check(_lib.hip().p2m_body_forward(
+                _p(pose), _p(t.get("pose_mean")), _p(t["betas"] if betas is None else betas), int(betas is not None),
+                _p(trans), -1 if trans is not None else model.center_joint, model.scale, B, model.V, model.J, model.nb,
+                _p(t["tmpl"]), _p(t["dirs"]), _p(t["wt"]), _p(t["jt"]), _p(t["js"]), _p(t["parents"]), _p(t["jslot"]), model.NJ,
+                _p(t.get("tip_vert")), _p(t.get("tip_slot")), model.n_tips, _p(t.get("xr_ptr")), _p(t.get("xr_idx")),
+                _p(t.get("xr_val")), model.JX, _p(ws), ws.numel() * 4, _p(verts), _p(joints), _p(extra), _stream()),
+                "p2m_body_forward")
+        ctx.model, ctx.ws = model, ws
+        ctx.save_for_backward(pose, betas, trans)
+        ctx.set_materialize_grads(False)
+        return (verts, joints, extra) if model.JX else (verts, joints)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_verts, g_joints, g_extra=None):
+        model, ws = ctx.model, ctx.ws
+        pose, betas, trans = ctx.saved_tensors
+        need = ctx.needs_input_grad[1:]
+        ups = [None if g is None else (g if g.dtype == torch.float32 else g.float()).contiguous()
+               for g in (g_verts, g_joints, g_extra)]
+        if not any(need) or all(g is None for g in ups):
+            return None, None, None, None
+        B, dev = int(pose.shape[0]), pose.device
+        t, tg = model._device_tables(dev), model._grad_tables(dev)
+        nbytes = int(_lib.hip().p2m_body_backward_workspace(B, model.V, model.J, model.nb))
+        if nbytes < 0:
+            raise _lib.P2MError("p2m_body_backward_workspace: bad shape")
+        part = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
+        outs = [torch.empty_like(x) if n else None for x, n in zip((pose, betas, trans), need)]
+        with torch.cuda.device(dev):
+            _lib.check(_lib.hip().p2m_body_backward(
+                _p(pose), _p(t.get("pose_mean")), _p(t["betas"] if betas is None else betas), int(betas is not None),
+                int(trans is not None), -1 if trans is not None else model.center_joint, model.scale, B, model.V, model.J,
+                model.nb, _p(t["tmpl"]), _p(t["dirs"]), _p(tg["dirs_t"]), _p(t["wt"]), _p(t["jt"]), _p(t["js"]),
+                _p(t["parents"]), _p(t["jslot"]), model.NJ, _p(t.get("tip_vert")), _p(t.get("tip_slot")), model.n_tips,
+                _p(tg.get("xc_ptr")), _p(tg.get("xc_idx")), _p(tg.get("xc_val")), model.JX, _p(ws), ws.numel() * 4,
+                _p(ups[0]), _p(ups[1]), _p(ups[2]), _p(part), part.numel() * 4, _p(outs[0]), _p(outs[1]), _p(outs[2]),
+                _stream()), "p2m_body_backward")
+        return None, outs[0], outs[1], outs[2]
+
+
+class BodyLayer(torch.nn.Module):
+    """layer = BodyLayer(model);  verts, joints[, extra] = layer(pose, betas=None, trans=None)
+
+    The differentiable entry of a BodyModel: the same inputs, input rules and forward kernels (the values are bitwise those
+    of model(pose, betas, trans)), but the outputs are new tensors per call, attached to one autograd function whose backward
+    is one p2m_body_backward call.  Gradients reach pose, betas and trans - whichever require grad; the model tables are
+    not trainable and the layer has no parameters.  betas=None takes the stored betas, trans=None centres on center_idx.
+    Any subset of the outputs may be used downstream.  Double backward is not supported.  Every launch is on the current
+    stream without a host synchronisation and all memory comes from torch's allocator, so forward plus backward can be
+    captured with torch.cuda.graph.  The first differentiable call uploads a vertex-major copy of the direction table (as
+    large as the table itself: 18 MB at SMPL size)."""
+
+    def __init__(self, model):
+        super().__init__()
+        if not isinstance(model, BodyModel):
+            raise TypeError("BodyLayer wraps a BodyModel")
+        self.model = model
+
+    def forward(self, pose, betas=None, trans=None):
+        m = self.model
+        if not isinstance(pose, torch.Tensor) or not pose.is_cuda:
+            raise _lib.P2MError("pose: the body-model kernels need a CUDA tensor (there is no CPU path)")
+        if pose.dim() != 2 or pose.shape[0] < 1:
+            raise ValueError(f"pose: expected axis-angle [B >= 1, {3 * m.J}] (rotation-matrix and 6-D poses are not "
+                             f"supported), got {list(pose.shape)}")
+        B = int(pose.shape[0])
+        pose = _cuda_f32(pose, "pose", (B, 3 * m.J), grad_ok=True)
+        if betas is not None:
+            betas = _cuda_f32(betas, "betas", (B, m.nb), grad_ok=True)
+        if trans is not None:
+            trans = _cuda_f32(trans, "trans", (B, 3), grad_ok=True)
+        for x, n in ((betas, "betas"), (trans, "trans")):
+            if x is not None and x.device != pose.device:
+                raise ValueError(f"{n} is on {x.device}, pose on {pose.device}")
+        return _BodyFunction.apply(m, pose, betas, trans)

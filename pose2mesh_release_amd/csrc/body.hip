@@ -18,15 +18,9 @@
 // Plain fp32 fmaf on the VALU, every output element accumulated in one fixed order by one thread whose instruction
 // sequence does not depend on the batch size or on the sample's slot in its tile: a sample's result is bitwise the same
 // in any batch.
-#include "p2m_common.h"
+#include "p2m_body.h"
 
 namespace p2m {
-
-constexpr int BODY_VT = 64;                 // vertices per block of k_body_skin
-constexpr int BODY_NT = BODY_VT * 3;        // threads: one per vertex component
-constexpr int BODY_TB = 8;                  // samples per block
-constexpr int BODY_JMAX = 64;               // chain joints / joints of the extra regressor
-constexpr int BODY_KMAX = 640;              // coefficients: nb + 9 (J - 1) (SMPL 217, MANO 145)
 
 struct BodyArgs {
   // inputs
@@ -55,7 +49,6 @@ struct BodyArgs {
   float* joints;             // [B, NJ, 3]
 };
 
-__host__ __device__ inline int body_ws_floats(int J, int K) { return ((K + 3) / 4) * 4 + 12 * J + 4; }
 // dynamic LDS of k_body_skin in bytes: at J = 64, K = 640 it is 51.3 KB, under the 64 KB a block may have
 static inline size_t body_skin_lds(int J, int K) {
   return sizeof(float) * ((size_t)((K + 3) / 4) * 4 * BODY_TB + (size_t)BODY_TB * 12 * J + BODY_TB * BODY_NT + BODY_TB * 4);
