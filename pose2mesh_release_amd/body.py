@@ -33,6 +33,12 @@ def _p(t):
     return None if t is None else _ct.c_void_p(t.data_ptr())
 
 
+def _betas_arg(t, betas):
+    """The betas pointer of a call: the input, or the model's stored betas.  With nb = 0 the input [B, 0] has no element and
+    so no address; the stored table's one-element stand-in goes instead (the kernels read nb values of it: none)."""
+    return _p(t["betas"] if betas is None or betas.numel() == 0 else betas)
+
+
 def _stream():
     return _ct.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -90,7 +96,8 @@ class BodyModel:
     == 0 - a host sync each.  Here trans=None centres (when center_idx is set) and a trans tensor is ALWAYS added;
     betas=None takes the model's stored betas and a betas tensor is always used.  So a batch whose translations are all
     exactly zero, with center_idx set, is centred by the reference and not here.  center_idx must name a chain joint
-    (centring on an appended tip vertex is not supported).
+    (centring on an appended tip vertex is not supported).  nb = 0, a model without a shape space, is allowed (J >= 2, so
+    that there is a coefficient at all): betas is then None or [B, 0], and BodyLayer's gradient for it is an empty [B, 0].
 
     The outputs are buffers reused per batch size, overwritten by the next call of the same size (as MeshEvaluator's
     are); clone what must outlive it.  Device tables are uploaded once per device.  Rest joints use J_regressor folded
@@ -203,7 +210,10 @@ class BodyModel:
 
     def _device_tables(self, dev):
         if self._dev is None or self._dev[0] != dev:
-            self._dev = (dev, {k: torch.from_numpy(_np.ascontiguousarray(v)).to(dev) for k, v in self._host.items()})
+            # a table without an element (nb = 0: the stored betas, the rest joints' shape directions) goes up as one zero
+            # that no kernel reads: an empty tensor has no address, and the C entries reject a null table
+            self._dev = (dev, {k: torch.from_numpy(_np.ascontiguousarray(v) if v.size else _np.zeros(1, v.dtype)).to(dev)
+                               for k, v in self._host.items()})
             self._bufs = {}
         return self._dev[1]
 
@@ -256,7 +266,7 @@ class BodyModel:
         buf = self._buffers(B, dev)
         with torch.cuda.device(dev):
             _lib.check(_lib.hip().p2m_body_forward(
-                _p(pose), _p(t.get("pose_mean")), _p(t["betas"] if betas is None else betas), int(betas is not None),
+                _p(pose), _p(t.get("pose_mean")), _betas_arg(t, betas), int(betas is not None),
                 _p(trans), -1 if trans is not None else self.center_joint, self.scale, B, self.V, self.J, self.nb,
                 _p(t["tmpl"]), _p(t["dirs"]), _p(t["wt"]), _p(t["jt"]), _p(t["js"]), _p(t["parents"]), _p(t["jslot"]), self.NJ,
                 _p(t.get("tip_vert")), _p(t.get("tip_slot")), self.n_tips, _p(t.get("xr_ptr")), _p(t.get("xr_idx")),
@@ -284,7 +294,7 @@ class _BodyFunction(torch.autograd.Function):
         extra = torch.empty((B, model.JX, 3), device=dev, dtype=torch.float32) if model.JX else None
         with torch.cuda.device(dev):
             _lib.check(_lib.hip().p2m_body_forward(
-                _p(pose), _p(t.get("pose_mean")), _p(t["betas"] if betas is None else betas), int(betas is not None),
+                _p(pose), _p(t.get("pose_mean")), _betas_arg(t, betas), int(betas is not None),
                 _p(trans), -1 if trans is not None else model.center_joint, model.scale, B, model.V, model.J, model.nb,
                 _p(t["tmpl"]), _p(t["dirs"]), _p(t["wt"]), _p(t["jt"]), _p(t["js"]), _p(t["parents"]), _p(t["jslot"]), model.NJ,
                 _p(t.get("tip_vert")), _p(t.get("tip_slot")), model.n_tips, _p(t.get("xr_ptr")), _p(t.get("xr_idx")),
@@ -300,11 +310,16 @@ class _BodyFunction(torch.autograd.Function):
     def backward(ctx, g_verts, g_joints, g_extra=None):
         model, ws = ctx.model, ctx.ws
         pose, betas, trans = ctx.saved_tensors
-        need = ctx.needs_input_grad[1:]
+        need = list(ctx.needs_input_grad[1:])
         ups = [None if g is None else (g if g.dtype == torch.float32 else g.float()).contiguous()
                for g in (g_verts, g_joints, g_extra)]
         if not any(need) or all(g is None for g in ups):
             return None, None, None, None
+        g_none = None
+        if need[1] and model.nb == 0:                        # no shape space: the gradient of [B, 0] betas has no element,
+            g_none, need[1] = torch.zeros_like(betas), False  # so the kernels are asked for the other gradients only
+            if not any(need):
+                return None, None, g_none, None
         B, dev = int(pose.shape[0]), pose.device
         t, tg = model._device_tables(dev), model._grad_tables(dev)
         nbytes = int(_lib.hip().p2m_body_backward_workspace(B, model.V, model.J, model.nb))
@@ -314,14 +329,14 @@ class _BodyFunction(torch.autograd.Function):
         outs = [torch.empty_like(x) if n else None for x, n in zip((pose, betas, trans), need)]
         with torch.cuda.device(dev):
             _lib.check(_lib.hip().p2m_body_backward(
-                _p(pose), _p(t.get("pose_mean")), _p(t["betas"] if betas is None else betas), int(betas is not None),
+                _p(pose), _p(t.get("pose_mean")), _betas_arg(t, betas), int(betas is not None),
                 int(trans is not None), -1 if trans is not None else model.center_joint, model.scale, B, model.V, model.J,
                 model.nb, _p(t["tmpl"]), _p(t["dirs"]), _p(tg["dirs_t"]), _p(t["wt"]), _p(t["jt"]), _p(t["js"]),
                 _p(t["parents"]), _p(t["jslot"]), model.NJ, _p(t.get("tip_vert")), _p(t.get("tip_slot")), model.n_tips,
                 _p(tg.get("xc_ptr")), _p(tg.get("xc_idx")), _p(tg.get("xc_val")), model.JX, _p(ws), ws.numel() * 4,
                 _p(ups[0]), _p(ups[1]), _p(ups[2]), _p(part), part.numel() * 4, _p(outs[0]), _p(outs[1]), _p(outs[2]),
                 _stream()), "p2m_body_backward")
-        return None, outs[0], outs[1], outs[2]
+        return None, outs[0], outs[1] if g_none is None else g_none, outs[2]
 
 
 class BodyLayer(torch.nn.Module):
