@@ -912,6 +912,66 @@ int p2m_camera_fit(const float* joints3d, const float* target, const float* weig
                    int32_t B, int32_t J, p2m_fit_schedule sched, int32_t steps, float img_res, double beta1, double beta2,
                    double eps, float* cam, float* loss, int32_t* status, void* stream);
 
+/* ---- Video evaluation: One-Euro smoothing and the per-video metrics (csrc/video.hip) ---------------------------------------
+ * The second half of the reference's 3DPW protocol (data/PW3D/dataset.py:383-417): smooth_pose (lib/smooth_utils.py), then
+ * compute_error_accel (lib/coord_utils.py:194-222), MPJPE and PA-MPJPE per video.  Launches on `stream` only, no allocation,
+ * no synchronisation (capturable).  tests/video_ref.py restates both entries in numpy.
+ *
+ * Sequences: seq_ptr [S + 1] int32 on the device, ascending from 0 to N; sequence s owns rows seq_ptr[s] .. seq_ptr[s + 1] - 1
+ * and may be empty.  The kernels clamp what they read from seq_ptr to [0, N].
+ *
+ * p2m_one_euro: the filter over a ragged batch.  x [N, C] fp32, a row is one frame of C scalars; rows [N] int32 or NULL: the
+ *   input row of frame i is x[rows[i]] (every entry must name a row of x), or x[i]; y [N, C] is written in sequence order and
+ *   may be x itself only when rows is NULL.  With f() = round to fp32, the parameters enter as
+ *     mc = f(min_cutoff), b = f(beta), te = f(dt), k2 = f(2 pi), kd = f(2 pi d_cutoff)   (that product taken in double)
+ *   and every operation below is one fp32 operation, rounded once and never fused; divisions are correctly rounded:
+ *     first frame of a sequence:  y = x,  xp = x,  dxp = 0
+ *     after that:  rd = kd te              ad = rd / (rd + 1)
+ *                  dx = (x - xp) / te      dxh = ad dx + (1 - ad) dxp
+ *                  cut = mc + b |dxh|      r = (k2 cut) te          a = r / (r + 1)
+ *                  y = a x + (1 - a) xp    xp = y,  dxp = dxh
+ *   This is OneEuroFilter.__call__ on float32 arrays as smooth_pose drives it (t_e = 1 there), bit for bit.  A NaN or an
+ *   infinity in one coordinate stays in that coordinate of that sequence.
+ *   Carried state (all three or none): state_x, state_dx [S, C] fp32 and started [S] int32.  started[s] == 0: the first frame
+ *   of sequence s in this call initialises the filter; otherwise (xp, dxp) continue from the state.  After the call the state
+ *   holds the last xp and dxp of every non-empty sequence and their started is 1; empty sequences keep theirs.  The flags are
+ *   written by a second launch on the stream, after the filter has read them.  Without state every sequence starts fresh.
+ *   One lane per (sequence, coordinate) with 4-byte accesses; 8- and 16-byte lane accesses where C and the alignment of x, y
+ *   and the state allow it AND the batch is large enough to fill the device at that width (csrc/video.hip);  loads run
+ *   p2m_one_euro_lookahead() frames ahead of the recurrence.
+ *   Errors (P2M_ERR_INVALID, nothing launched): NULL x, seq_ptr or y; N < 0, S < 1, C < 1; N C or S C >= 2^31; the state given
+ *   in part; rows together with y == x; a parameter that is not finite, dt <= 0, a cutoff < 0, or a parameter whose fp32
+ *   rounding is infinite (or 0, for dt).
+ *
+ * p2m_video_eval: the metrics of every video in one call.  pred, gt [N, J, 3] fp32 in sequence order, 1 <= J <= 64; vis [N]
+ *   uint8 or NULL (all visible).  Everything is accumulated in fp64 from the fp32 inputs and rounded once where stored as fp32.
+ *     accel [N], accel_valid [N] uint8: for frame i with i + 2 inside its sequence and vis[i], vis[i + 1], vis[i + 2] all
+ *       non-zero, mean_j |(p_i - 2 p_i+1 + p_i+2) - (g_i - 2 g_i+1 + g_i+2)|  (compute_error_accel; its np.roll wrap-around
+ *       never survives the [:-2]); elsewhere 0 and accel_valid = 0
+ *     mpjpe [N, J]: |p - g| per joint;   pa_mpjpe [N, J] (want_pa): the same after the similarity alignment of the frame's
+ *       prediction onto its ground truth, the solve of p2m_rigid_align (this unit is built without fma contraction, so the two
+ *       agree to the last bits of the fp64 solve, not bitwise)
+ *     frame_sums [N, 4] fp64, workspace and output: accel, accel_valid, sum_j mpjpe, sum_j pa_mpjpe per frame
+ *     seq_stats [S, 8] fp64: frames, valid accelerations, mean accel (NaN without one), mean of mpjpe over frames x joints (NaN
+ *       when empty), sum of pa_mpjpe, count of pa_mpjpe values (0 without want_pa), 0, 0
+ *     totals [8] fp64, the reference's aggregation: [0] accel error = unweighted mean over videos of the per-video means,
+ *       [1] MPJPE = unweighted mean over videos of the per-video means, [2] PA-MPJPE = mean pooled over all frames and joints,
+ *       [3] videos in [0], [4] videos left out of [0], [5] videos in [1], [6] empty videos, [7] frames
+ *   DIFFERENT from the reference on purpose: a video without a valid acceleration frame (fewer than 3 frames, or no visible
+ *   triple) has a NaN per-video value, and np.mean would make the reference's total NaN; here it is left out of totals[0] and
+ *   counted in totals[4].  Empty videos are left out of totals[1] in the same way and counted in totals[6].  A total over no
+ *   video is NaN.
+ *   Fixed reduction orders, no atomics: bitwise reproducible, and a sequence's results do not depend on the other sequences.
+ *   Errors (P2M_ERR_INVALID, nothing launched): NULL required pointers (pa_mpjpe is required with want_pa), N < 0, S < 1, J
+ *   outside [1, 64], N J 3 >= 2^31.                                                                                       */
+int32_t p2m_one_euro_lookahead(void);
+int p2m_one_euro(const float* x, const int32_t* seq_ptr, const int32_t* rows, int32_t N, int32_t S, int32_t C,
+                 double min_cutoff, double beta, double d_cutoff, double dt, float* state_x, float* state_dx, int32_t* started,
+                 float* y, void* stream);
+int p2m_video_eval(const float* pred, const float* gt, const int32_t* seq_ptr, const uint8_t* vis, int32_t N, int32_t S,
+                   int32_t J, int32_t want_pa, float* accel, uint8_t* accel_valid, float* mpjpe, float* pa_mpjpe,
+                   double* frame_sums, double* seq_stats, double* totals, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
