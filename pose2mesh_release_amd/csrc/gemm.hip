@@ -125,7 +125,15 @@ __device__ __forceinline__ void epi_group_rows(const int* rowtab, long m0, long 
 // Statistics: sums and M2 meet in two disjoint reduction buffers, two block barriers.  A wave whose columns all lie beyond N
 // (the upper half of a 64-wide tile at N = 32) skips every element loop and only attends the barriers.
 constexpr int EPI_BARRIERS = 2;     // block barriers of the statistics reduction (the staging waves of _ws attend them)
-template <int BN, bool EXTRA, bool ROWS>
+// LDS the epilogue takes from the front of the block's (free) staging buffers: the two reduction buffers, and behind them,
+// in the staged forms, two strips of 8 rows x BN / 2 columns for each of the four MFMA waves
+#ifndef P2M_EPI_COPYOUT_DEFAULT
+#define P2M_EPI_COPYOUT_DEFAULT true   // what P2M_EPI_COPYOUT is when the environment does not set it
+#endif
+constexpr int EPI_STRIP_ROWS = 8;
+constexpr int EPI_RED_WORDS(int BN) { return 4 * BN; }
+constexpr int EPI_LDS_WORDS(int BN, bool CO) { return EPI_RED_WORDS(BN) + (CO ? 4 * 2 * EPI_STRIP_ROWS * (BN / 2) : 0); }
+template <int BN, bool EXTRA, bool ROWS, bool CO = false, bool CO_STATS = CO>
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, floatx16 (&acc)[2][BN / 64], float* smem,
                                               const int* rowtab, int mt, long m0, int n0, int rs_i0, int wm, int wn,
                                               int l31, int lhi, int descale = 0) {
@@ -136,7 +144,10 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, floatx16 (&acc)
   // C/D layout of 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
   const int wnu = __builtin_amdgcn_readfirstlane(wn);                      // (wave-uniform, and known to be)
   const bool live = n0 + wnu * WTN < g.N;                                  // wave-uniform
-  const bool wst = ROWS && g.row_w != nullptr && g.stats != nullptr;      // weighted partials (block-uniform)
+  // CO without CO_STATS: a staged form that is never launched with statistics (k_gemm_planes_ws at its 128-register bound) -
+  // no statistics walk, no M2 pass, nothing kept
+  const bool has_stats = (!CO || CO_STATS) && g.stats != nullptr;         // block-uniform
+  const bool wst = ROWS && g.row_w != nullptr && has_stats;               // weighted partials (block-uniform)
   const float* wtab = reinterpret_cast<const float*>(rowtab + BM);
   const int mlw = wm * 64 + 4 * lhi;   // first tile row of the lane; group gi adds (gi >> 2) * 32 + (gi & 3) * 8
   float csum[TN];
@@ -161,7 +172,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, floatx16 (&acc)
     bool cok[TN];
     unsigned c4[TN];                   // byte offset of the column inside its output plane
     char* Cb[TN];                      // uniform: output plane of the wave's 32 columns, at the block's first row
-    const bool pair = EXTRA && !ROWS && g.pair_out;
+    const bool pair = !CO && EXTRA && !ROWS && g.pair_out;            // (the pair sums are launched with CO off)
     const long rowbase = ROWS ? (long)(mt / g.tps) * g.V : m0;            // uniform: the rows of this block start here
     const int rowbase32 = (int)rowbase;                                   // (ROWS: the row table holds ints)
     const unsigned pitch = (unsigned)g.Nc * 4u;
@@ -294,8 +305,151 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, floatx16 (&acc)
         __builtin_amdgcn_sched_barrier(0);
       }
     };
+    // The staged copy-out (round 9, CO).  The value chain per element is the walk's; a wave writes the values of a row group -
+    // 8 consecutive tile rows x its WTN columns - into a strip of its own (ds_write_b32), reads the strip back as 16-byte row
+    // segments and stores those: lane -> (strip row lane >> 3, column quad lane & 7 of the 32-column tile j), so a store
+    // instruction covers eight rows of 128 contiguous bytes, and the output plane of a store is uniform as in the walk.  Two
+    // strips per wave: the reads of group gi are in flight while the values of group gi + 1 are staged; the wave's own LDS
+    // wait stands between its writes and its reads, no block barrier.
+    // Banks.  ds_write_b32 (two 32-lane halves, bank = dword % 32): a half writes the 32 consecutive dwords of one strip row
+    // and one tile j - every bank once, whatever the row stride.  ds_read_b128 (four 16-lane groups, e.g. lanes {0-3, 12-15,
+    // 20-27}, bank = dword % 64): a group reads quads 0-3 of strip row 0, quads 4-7 of rows 1 and 2, quads 0-3 of row 3 (the
+    // other groups likewise).  WTN = 32: the row stride of 32 dwords puts these at dwords 0-15, 48-63, 80-95 = 16-31, 96-111 =
+    // 32-47 mod 64: every bank once.  WTN = 64: the stride is 0 mod 64 and rows 1 and 2 would meet, so tile j of strip row s
+    // lies in the half j ^ (s & 1) of its row: dwords 0-15, 64 + 32 + 16.. = 48-63, 128 + 16.. = 16-31, 192 + 32.. = 32-47.
+    // The addend (never together with statistics here) is loaded in the copy-out layout one group ahead of the stores, before
+    // the stores of the group in front of it, and added at copy-out: v + addend is the same sum whichever lane forms it.  The
+    // maximum is formed at copy-out over the values stored; the sums keep their lanes and their order (KEEP, as in the walk).
+    auto walk_co = [&](auto add_tag, auto keep_tag) {
+      constexpr bool ADD = decltype(add_tag)::value;
+      constexpr bool KEEP = decltype(keep_tag)::value;
+      static_assert(!(ADD && KEEP), "statistics with an addend keep the 4-byte walk");
+      constexpr int SB = EPI_STRIP_ROWS * WTN;                               // words of one strip
+      float* const strip = smem + EPI_RED_WORDS(BN) + (wm * 2 + wnu) * 2 * SB;
+      // (opaque: what the copy-out derives from the lane is formed here, not in front of the k loop and carried through it)
+      int lane = lhi * 32 + l31;
+      asm volatile("" : "+v"(lane));
+      const int srow = lane >> 3;
+      const unsigned col16 = (unsigned)(lane & 7) * 16u;
+      float* const wr = strip + (lane >> 5) * 4 * WTN + (lane & 31);
+      const int rd0 = srow * WTN + (TN == 2 ? (srow & 1) * 32 : 0) + (lane & 7) * 4;
+      const float* rd[TN];
+      char* Cc[TN];                      // uniform: Cb + the first column of tile j inside its plane
+      const char* Ac[TN];
+      bool ju[TN];                       // uniform: tile j lies inside N (N % 32 == 0: all of its columns or none)
+#pragma unroll
+      for (int j = 0; j < TN; j++) {
+        const int nu = n0 + wnu * WTN + j * 32;
+        const int q = (nu >= g.Nc ? 1 : 0) + (nu >= 2 * g.Nc ? 1 : 0);
+        ju[j] = nu < g.N;
+        Cc[j] = Cb[j] + (unsigned)(nu - q * g.Nc) * 4u;
+        Ac[j] = Ab + (ADD && ju[j] ? (unsigned)nu * 4u : 0u);
+        rd[j] = strip + (rd0 ^ (j * 32));
+      }
+      // byte offset of the lane's 16 bytes in the row it copies out of group gi, from the block's first row, or NOROW
+      auto co_row = [&](int gi) {
+        const int tr = wm * 64 + (gi >> 2) * 32 + (gi & 3) * 8 + srow;
+        unsigned ro;
+        if (ROWS) {
+          const int rl = rowtab[tr];
+          ro = rl >= 0 ? (unsigned)(rl - rowbase32) * pitch + col16 : NOROW;
+        } else {
+          ro = m0 + tr < g.M ? (unsigned)tr * pitch + col16 : NOROW;
+        }
+        asm volatile("" : "+v"(ro));     // (opaque, as in the walk)
+        return ro;
+      };
+      f32x4 cp[TN];
+      f32x4 ad[2][ADD ? TN : 1];
+      unsigned ro_cur = NOROW, ro_nxt = co_row(0);
+#pragma unroll
+      for (int j = 0; j < TN; j++) asm volatile("" : "+v"(bias_v[j]), "+v"(sc_v[j]), "+v"(sh_v[j]));
+      // values of group gi -> strip gi & 1 (and, KEEP, the sums); the addend of the group is requested first
+      auto stage = [&](int gi) {
+        if constexpr (ADD) {             // (a row or a tile that does not exist reads the block's first row / column)
+          const unsigned lo = ro_nxt != NOROW ? ro_nxt : col16;
+#pragma unroll
+          for (int j = 0; j < TN; j++) ad[gi & 1][j] = *reinterpret_cast<const f32x4*>(Ac[j] + lo);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        const int i = gi >> 2, r0 = (gi & 3) * 4;
+        unsigned ro4[4] = {0u, 0u, 0u, 0u};
+        f32x4 w4 = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (KEEP) {
+          row_offsets(gi, ro4);
+          if (wst) w4 = *reinterpret_cast<const f32x4*>(wtab + mlw + i * 32 + (gi & 3) * 8);
+        }
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+#pragma unroll
+          for (int j = 0; j < TN; j++) {
+            const int r = r0 + e;
+            float v = __builtin_ldexpf(val[i][j][r], descale) + bias_v[j];     // descale: exact (two-fp16-slice mode), else 0
+            if (g.act_scale != nullptr) v = fmaf(v, sc_v[j], sh_v[j]);
+            if (g.act_relu) v = fmaxf(v, 0.f);
+            asm volatile("" : "+v"(v));
+            if constexpr (KEEP) {
+              val[i][j][r] = v;
+              const float term = wst ? w4[e] * v : v;
+              csum[j] += (ro4[e] != NOROW && cok[j]) ? term : 0.f;
+            }
+            wr[(gi & 1) * SB + e * WTN + (TN == 2 ? (j ^ (e & 1)) * 32 : 0)] = v;
+          }
+        if constexpr (KEEP) {
+#pragma unroll
+          for (int j = 0; j < TN; j++) asm volatile("" : "+v"(csum[j]));
+        }
+      };
+      // strip gi & 1 -> registers, in the copy-out layout, with the row of the lane; the row of the next group is asked for
+      // in front of the strip (LDS returns in order: the next group's addend request waits for the row only)
+      auto fetch = [&](int gi) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the wave's own strip writes, before it reads them
+        ro_cur = ro_nxt;
+        if (gi + 1 < NG) ro_nxt = co_row(gi + 1);
+#pragma unroll
+        for (int j = 0; j < TN; j++) cp[j] = *reinterpret_cast<const f32x4*>(rd[j] + (gi & 1) * SB);
+      };
+      auto copy_out = [&](int gi) {
+#pragma unroll
+        for (int j = 0; j < TN; j++) {
+          f32x4 v = cp[j];
+          if constexpr (ADD) v += ad[gi & 1][j];
+          const bool ok = ro_cur != NOROW && ju[j];
+          if (ok) *reinterpret_cast<f32x4*>(Cc[j] + ro_cur) = v;
+          const float m4 = fmaxf(fmaxf(amax_abs(v[0]), amax_abs(v[1])), fmaxf(amax_abs(v[2]), amax_abs(v[3])));
+          vmax = fmaxf(vmax, ok ? m4 : 0.f);
+        }
+        asm volatile("" : "+v"(vmax));
+      };
+      // without statistics the copy-out of a group runs one group behind its staging (its strip reads are in flight meanwhile);
+      // with them (the 64 values stay in registers for the M2 pass) a group is staged, read back and stored in turn: eight
+      // registers less across the walk
+      constexpr bool PIPE = !KEEP;
+#pragma unroll
+      for (int gi = 0; gi <= NG; gi++) {
+        if (gi < NG) stage(gi);
+        if constexpr (PIPE) {
+          if (gi >= 1) copy_out(gi - 1);
+          if (gi < NG) fetch(gi);
+        } else if (gi < NG) {
+          fetch(gi);
+          copy_out(gi);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    };
     const bool add = EXTRA && g.addend != nullptr;
-    if (g.stats != nullptr) {
+    if constexpr (CO) {
+      // the staged forms (never launched for pair sums); statistics together with an addend (no launch of the train step) keep
+      // the 4-byte walk
+      if (has_stats) {
+        if (add) walk(std::true_type{}, std::true_type{});
+        else walk_co(std::false_type{}, std::true_type{});
+      } else {
+        if (add) walk_co(std::true_type{}, std::false_type{});
+        else walk_co(std::false_type{}, std::false_type{});
+      }
+    } else if (has_stats) {
       if (add) walk(std::true_type{}, std::true_type{});
       else walk(std::false_type{}, std::true_type{});
     } else {
@@ -304,7 +458,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, floatx16 (&acc)
     }
   }
 
-  if (g.stats != nullptr) {
+  if (has_stats) {
     // column sums over the 128-row tile: lane^32 holds the same column, the other wm wave the other 64 rows
     float* red = smem;             // [2 (wm)][BN] sums      (safe: all waves passed the last __syncthreads of the k loop)
     float* red2 = smem + 2 * BN;   // [2 (wm)][BN] M2
@@ -536,7 +690,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_planes(GemmArgs g) {
 //  (-1.4 % on the step), the BatchNorm-backward reduction in this kernel's epilogue (its 4-byte strided reads of the
 //  layer's raw input cost the contraction +4.5 ms, the pass they replace 3.3 ms).)
 // ---------------------------------------------------------------------------------------------
-template <int BN, bool EXTRA, bool ROWS, int NS>
+template <int BN, bool EXTRA, bool ROWS, int NS, bool CO>
 // Round 6: the ROW-SET instantiations are held to 128 registers (launch bound 4 waves per SIMD = TWO blocks per CU, as this
 // header always assumed): hipcc gave the 128-wide ones 152-174 - one block per CU, one MFMA wave per SIMD and nothing to
 // cover its fragment reads and barriers.  At 128 the epilogue spills 28-46 dwords per lane (none in the k loop) and
@@ -544,6 +698,10 @@ template <int BN, bool EXTRA, bool ROWS, int NS>
 // 103 us; the plain-row ones measured 4 % slower that way and keep their bound (same-box rocprofv3 --stats, 9 steps).
 __global__ __launch_bounds__(512, (BN == 128 && ROWS) ? 4 : 2) void k_gemm_planes_ws(GemmArgs g) {
   constexpr int KB = 16;
+  // the staged row-set forms at 128 registers are not launched with statistics (launch_gemm_planes): next to the 64 values kept
+  // for the M2 pass the staged walk spills more than the 4-byte one (192 against 148-152 bytes per lane), and without any
+  // statistics code these forms need no scratch at all
+  constexpr bool CO_STATS = CO && !(BN == 128 && ROWS);
   typedef typename SliceFrag<NS>::type frag_t;
   constexpr int NBUF = 2, NST = 2;    // LDS ring of two chunks, two register stages of lead (three: no change, round 6)
   constexpr int AHEAD = NBUF - 1;     // the producers store chunk kc + AHEAD during iteration kc
@@ -556,6 +714,8 @@ __global__ __launch_bounds__(512, (BN == 128 && ROWS) ? 4 : 2) void k_gemm_plane
   constexpr int A_BUF = NS * BM * LDX;
   constexpr int B_BUF = NS * BN * LDX;
   constexpr int SM_WORDS = NBUF * (A_BUF + B_BUF) / 2 + (ROWS ? ROWTAB_WORDS : 0);
+  static_assert(EPI_LDS_WORDS(BN, CO) <= NBUF * (A_BUF + B_BUF) / 2,
+                "the epilogue's reduction buffers and copy-out strips live in the ring, in front of the row table");
   __shared__ __attribute__((aligned(16))) float smem[SM_WORDS];
   __shared__ __attribute__((aligned(16))) float actco[2 * 256];        // activation on load: scale | shift of plane 0's columns
   unsigned short* As = reinterpret_cast<unsigned short*>(smem);
@@ -780,9 +940,9 @@ __global__ __launch_bounds__(512, (BN == 128 && ROWS) ? 4 : 2) void k_gemm_plane
   }
   __syncthreads();   // staging buffers are free: the epilogue reuses them
   if (!producer) {
-    gemm_epilogue<BN, EXTRA, ROWS>(g, acc, smem, rowtab, mt, m0, n0, rs_i0, wm, wn, l31, lhi, descale);
+    gemm_epilogue<BN, EXTRA, ROWS, CO, CO_STATS>(g, acc, smem, rowtab, mt, m0, n0, rs_i0, wm, wn, l31, lhi, descale);
   } else {
-    if (g.stats != nullptr) {                   // the block barriers of the statistics reduction
+    if ((!CO || CO_STATS) && g.stats != nullptr) {        // the block barriers of the statistics reduction
 #pragma unroll
       for (int b = 0; b < EPI_BARRIERS; b++) __syncthreads();
     }
@@ -818,7 +978,7 @@ __device__ unsigned long long g_k1_tr[4096][4];
 #define P2M_K1T(ev) do { } while (0)
 #endif
 
-template <int BN, bool EXTRA, int NS, int KP>
+template <int BN, bool EXTRA, int NS, int KP, bool CO>
 __global__ __launch_bounds__(256, 2) void k_gemm_rows_k1(GemmArgs g) {
   typedef typename SliceFrag<NS>::type frag_t;
   constexpr bool ROWS = true;
@@ -832,7 +992,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_rows_k1(GemmArgs g) {
   constexpr int KSTEPS = KP / 16;         // MFMA k steps per pass (2 or 4: the B double buffer's parity is static)
   constexpr int A_IMG = NS * BM * LDX;    // bf16 / fp16 elements
   static_assert(KP == 64 || KP == 32, "pass width");
-  static_assert(A_IMG / 2 >= 4 * BN, "the epilogue's two reduction buffers live in the image");
+  static_assert(A_IMG / 2 >= EPI_LDS_WORDS(BN, CO),
+                "the epilogue's two reduction buffers and its copy-out strips live in the image, in front of the row table");
   __shared__ __attribute__((aligned(16))) float smem[A_IMG / 2 + ROWTAB_WORDS];
   __shared__ __attribute__((aligned(16))) float actco[2 * 256];
   unsigned short* As = reinterpret_cast<unsigned short*>(smem);
@@ -1008,7 +1169,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_rows_k1(GemmArgs g) {
   }
   P2M_K1T(2);
   __syncthreads();   // the image is free: the epilogue's reduction reuses it
-  gemm_epilogue<BN, EXTRA, ROWS>(g, acc, smem, rowtab, mt, m0, n0, rs_i0, wm, wn, l31, lhi, descale);
+  gemm_epilogue<BN, EXTRA, ROWS, CO>(g, acc, smem, rowtab, mt, m0, n0, rs_i0, wm, wn, l31, lhi, descale);
   P2M_K1T(3);
 }
 
@@ -2119,18 +2280,34 @@ static bool rows_k1() {
   static const bool v = [] { const char* e = getenv("P2M_ROWS_K1"); return e ? atoi(e) != 0 : true; }();
   return v;
 }
+// P2M_EPI_COPYOUT (read once per process): 1 = the slice-arithmetic contractions copy their output
+// tile out through wave-private LDS strips with 16-byte stores (gemm_epilogue<.., CO = true>); 0 = the 4-byte walk.  Bitwise the
+// same results.  The staged forms need every output plane, and the addend, 16-byte aligned (rows then are: Nc % 32 == 0); a
+// launch that is not takes the walk, as do the pair-sum launches.
+static bool epi_copyout() {
+  static const bool v = [] { const char* e = getenv("P2M_EPI_COPYOUT"); return e ? atoi(e) != 0 : P2M_EPI_COPYOUT_DEFAULT; }();
+  return v;
+}
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <bool ROWS>
 static void launch_gemm_planes(GemmArgs& g, bool extra, hipStream_t s) {
   const bool wide = (g.N % 128 == 0);
   g.ntn = wide ? g.N / 128 : cdiv(g.N, 64);
   const dim3 grid(cdiv(g.ntm, 8) * 8 * g.ntn);
+  const bool co = epi_copyout() && !g.pair_out && aligned16(g.C[0]) && aligned16(g.C[1]) && aligned16(g.C[2]) &&
+                  aligned16(g.addend);              // (planes that are not there are NULL)
   if constexpr (ROWS) {
     if (g.nplanesA == 1 && g.Ka <= 256 && g.Bx != nullptr && rows_k1()) {
 #define P2M_LAUNCH_K1(BNv, EX, KPv)                                                                          \
   do {                                                                                                      \
-    if (g.a_amax != nullptr) hipLaunchKernelGGL((k_gemm_rows_k1<BNv, EX, 2, KPv>), grid, dim3(256), 0, s, g); \
-    else hipLaunchKernelGGL((k_gemm_rows_k1<BNv, EX, 3, KPv>), grid, dim3(256), 0, s, g);                    \
+    if (g.a_amax != nullptr) {                                                                              \
+      if (co) hipLaunchKernelGGL((k_gemm_rows_k1<BNv, EX, 2, KPv, true>), grid, dim3(256), 0, s, g);        \
+      else hipLaunchKernelGGL((k_gemm_rows_k1<BNv, EX, 2, KPv, false>), grid, dim3(256), 0, s, g);          \
+    } else {                                                                                                \
+      if (co) hipLaunchKernelGGL((k_gemm_rows_k1<BNv, EX, 3, KPv, true>), grid, dim3(256), 0, s, g);        \
+      else hipLaunchKernelGGL((k_gemm_rows_k1<BNv, EX, 3, KPv, false>), grid, dim3(256), 0, s, g);          \
+    }                                                                                                       \
   } while (0)
 #define P2M_LAUNCH_K1_KP(BNv, EX) \
   do { if (g.Ka % 64 == 0) P2M_LAUNCH_K1(BNv, EX, 64); else P2M_LAUNCH_K1(BNv, EX, 32); } while (0)
@@ -2142,10 +2319,17 @@ static void launch_gemm_planes(GemmArgs& g, bool extra, hipStream_t s) {
     }
   }
   if (g.Bx != nullptr) {
+    // (the 128-wide row-set forms have no staged walk with statistics: k_gemm_planes_ws)
+    const bool co_ws = co && !(ROWS && wide && g.stats != nullptr);
 #define P2M_LAUNCH_WS(BNv, EX)                                                                              \
   do {                                                                                                      \
-    if (g.a_amax != nullptr) hipLaunchKernelGGL((k_gemm_planes_ws<BNv, EX, ROWS, 2>), grid, dim3(512), 0, s, g); \
-    else hipLaunchKernelGGL((k_gemm_planes_ws<BNv, EX, ROWS, 3>), grid, dim3(512), 0, s, g);                 \
+    if (g.a_amax != nullptr) {                                                                              \
+      if (co_ws) hipLaunchKernelGGL((k_gemm_planes_ws<BNv, EX, ROWS, 2, true>), grid, dim3(512), 0, s, g);  \
+      else hipLaunchKernelGGL((k_gemm_planes_ws<BNv, EX, ROWS, 2, false>), grid, dim3(512), 0, s, g);       \
+    } else {                                                                                                \
+      if (co_ws) hipLaunchKernelGGL((k_gemm_planes_ws<BNv, EX, ROWS, 3, true>), grid, dim3(512), 0, s, g);  \
+      else hipLaunchKernelGGL((k_gemm_planes_ws<BNv, EX, ROWS, 3, false>), grid, dim3(512), 0, s, g);       \
+    }                                                                                                       \
   } while (0)
     if (wide) { if (extra) P2M_LAUNCH_WS(128, true); else P2M_LAUNCH_WS(128, false); }
     else { if (extra) P2M_LAUNCH_WS(64, true); else P2M_LAUNCH_WS(64, false); }
