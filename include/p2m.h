@@ -972,6 +972,65 @@ int p2m_video_eval(const float* pred, const float* gt, const int32_t* seq_ptr, c
                    int32_t J, int32_t want_pa, float* accel, uint8_t* accel_valid, float* mpjpe, float* pa_mpjpe,
                    double* frame_sums, double* seq_stats, double* totals, void* stream);
 
+/* ---- 2D pose overlay: batched anti-aliased lines, discs and rings on uint8 images (csrc/overlay.hip) -------------------------
+ * The device counterpart of lib/vis.py's vis_2d_keypoints (:77-113; vis_2d_pose is the same on an image) and
+ * vis_coco_skeleton (:10-74).  GEOMETRY AND SEMANTICS follow the reference: which primitives are drawn, where, in which order,
+ * with which thickness, on a copy that is then blended with the image.  THE PIXEL ARITHMETIC is this project's: the reference
+ * draws with OpenCV's LINE_AA tables, and OpenCV is not a dependency here, so this comment is the contract and
+ * tests/overlay_ref.py its exact-integer restatement.  It is held bit for bit; parity with OpenCV's pixels is not claimed.
+ * INPUTS, device memory unless stated:
+ *   poses    fp32 [B, P, J, C], C = 2 or 3: x, y in pixels of image b, then an optional confidence.  Image b receives its P
+ *            people in index order (the demo's crowd loop is B = 1, a batch of crops P = 1)
+ *   bones    int32 [L, 2] joint indices (NULL allowed when L = 0)
+ *   colours  uint8, in the image's own channel order (the kernels never swap channels); colour_mode 0: [L, 3], one per bone
+ *            (vis_2d_keypoints);  1: [B, P, 3], one per person (vis_coco_skeleton's given_color).  NULL allowed when L = 0
+ *   boxes    fp32 [B, P, 4, 2] or NULL: the four corners of vis_2d_keypoints' bbox;  box_rgb: HOST value, channel 0 in bits
+ *            0-7, channel 1 in bits 8-15, channel 2 in bits 16-23
+ *   src, dst uint8 [B, H, W, 3].  src == dst is allowed and is the normal use; when they differ every pixel of dst is written
+ *            (they must then not overlap).  Rows are 3 W bytes at any byte offset: 4-byte accesses are used for a lane's 12
+ *            bytes where they are 4-byte aligned, single bytes elsewhere
+ *   thr      host float;  line_h2, mark_h2, box_h2: host, thickness in HALF pixels, in [0, 64] (h2 = 2 is OpenCV's thickness 2,
+ *            a filled radius-3 disc is h2 = 6);  mark_r16: host, -1 a disc, >= 0 a ring of radius r16 / 16 pixels, at most
+ *            1024;  alpha256: host, in [0, 256]
+ *   status   int32 [B, P] or NULL, written (not accumulated) by every call
+ * SNAPPING.  A coordinate v becomes the integer (int)v, truncated towards zero (vis.py's astype(np.int32)).  A joint is
+ * UNUSABLE when a coordinate is not finite or |v| >= 16384: status bit 0 of its person is set (for any of the person's J
+ * joints, used by a bone or not) and the joint is invisible.  A joint is VISIBLE iff it is usable and, with C = 3, conf > thr
+ * (strict; a NaN confidence is invisible).  Pixel (row i, column j) is the point (j, i), as in OpenCV.  A box with an unusable
+ * corner is skipped as a whole and status bit 1 is set.
+ * PRIMITIVES AND PAINT ORDER within an image: persons p = 0 .. P - 1; for each, with boxes, the four box edges corner k ->
+ * corner (k + 1) mod 4 (thickness box_h2, colour box_rgb); then for each bone l = 0 .. L - 1 (i1, i2) three primitives:
+ * the line i1 - i2 (line_h2) iff both joints are visible, the mark at i1 iff i1 is visible, the mark at i2 iff i2 is visible
+ * (mark_h2, mark_r16).  That is the order of vis.py's loops; a later primitive paints over an earlier one.  A bone index
+ * outside [0, J) is an error of the caller: this entry cannot see device memory, so the check belongs to the owner of the
+ * host copy (overlay.PoseOverlay refuses at construction); the kernels never follow such an index, the bone draws nothing.
+ * COVERAGE, exact.  Pixel q, segment a - b (a mark: a = b), all integers: d = b - a, w = q - a, L2 = d.d, t = w.d.
+ *   L2 = 0 or t <= 0:  (num, den) = (w.w, 1);    t >= L2:  (num, den) = (|q - b|^2, 1);
+ *   otherwise, with c = w.x d.y - w.y d.x:       (num, den) = (c^2, L2)
+ *   D = floor(16 sqrt(num / den)) = the unique integer with D^2 den <= 256 num < (D + 1)^2 den;   a ring: D <- |D - r16|
+ *   cov = clamp(8 h2 + 8 - D, 0, 16) sixteenths: clamp(h + 1/2 - dist, 0, 1) on a 1/16 grid, within 1/16 of the analytic value
+ * D only matters below 8 h2 + 8 + r16 <= 1544, so the kernel estimates it in fp32 and settles it with the two exact 64-bit
+ * comparisons; |c| >= 2^26 is more than 1400 pixels from the line (cov = 0), and below that 256 c^2 fits 64 bits.  No square
+ * root and no division is named, so nothing rests on how either is rounded.
+ * BLENDING, exact integers per channel: m = src; for each primitive in paint order with cov > 0:
+ *   m <- m + (((colour - m) cov + 8) >> 4)      (arithmetic shift: a floor)
+ * and at the end dst = (src (256 - alpha256) + m alpha256 + 128) >> 8, cv2.addWeighted(img, 1 - alpha, kp_mask, alpha):
+ * alpha256 = 256 gives m, 0 gives src.
+ * Two kernels on `stream`, always the same two: no allocation, no memset, no synchronisation, no data-dependent grid, no
+ * float atomics and no atomics in global memory - capturable, reproducible bit for bit, and an image's pixels do not depend on
+ * the batch around it.  A 32 x 32-pixel tile that no primitive's inflated bbox meets is not touched when src == dst.
+ *   workspace  p2m_pose_overlay_workspace(B, P, L, with_boxes) bytes of device memory, 16-byte aligned: 24 bytes per slot
+ * Errors (P2M_ERR_INVALID, nothing launched): a NULL required pointer (poses, src, dst, workspace; bones and colours when
+ * L > 0), B < 0, H or W outside [1, 8192], J or P outside [1, 64], L outside [0, 64], L = 0 without boxes, C not 2 or 3, an
+ * h2 outside [0, 64], mark_r16 outside [-1, 1024], alpha256 outside [0, 256], an unknown colour_mode, B P (3 L + 4) >= 2^31,
+ * 2^31 tiles or more, a small or misaligned workspace.  B = 0 is a no-op.                                                   */
+enum { P2M_OVERLAY_COLOUR_PER_BONE = 0, P2M_OVERLAY_COLOUR_PER_PERSON = 1 };
+int p2m_pose_overlay_workspace(int32_t B, int32_t P, int32_t L, int32_t with_boxes, int64_t* bytes_out);
+int p2m_pose_overlay(const float* poses, int32_t B, int32_t P, int32_t J, int32_t C, const int32_t* bones, int32_t L,
+                     const uint8_t* colours, int32_t colour_mode, const float* boxes, uint32_t box_rgb, const uint8_t* src,
+                     uint8_t* dst, int32_t H, int32_t W, float thr, int32_t line_h2, int32_t mark_h2, int32_t mark_r16,
+                     int32_t box_h2, int32_t alpha256, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
