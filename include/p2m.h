@@ -785,6 +785,62 @@ int p2m_train_sample(const float* verts, const float* trans, float mesh_scale, c
                      float* lift_pose3d, float* reg_pose3d, float* mesh_valid, float* lift_valid, float* reg_valid,
                      int32_t* status, float* fit_err, int8_t* kind, float* rot_flip, void* stream);
 
+/* ---- dataset annotations -> camera-frame body parameters, and the gender bank's choice (csrc/annot.hip) -------------------
+ * What get_smpl_coord / get_mano_coord of the reference's datasets do per sample on the PARAMETERS, in numpy and
+ * transforms3d on a dataloader worker (data/Human36M/dataset.py:253-299, data/AMASS/dataset.py:182-213, data/FreiHAND/
+ * dataset.py:110-134; PW3D, SURREAL, MuCo and COCO are subsets), for a batch of row indices into annotation tables that
+ * live in device memory: one launch on `stream`; nothing allocates or synchronises.
+ * Tables, N rows each, fp32 unless noted: pose [N, 3 J], betas [N, nb] (NULL with nb = 0), trans [N, 3] (NULL: zeros), cam_R
+ * [N, 9] row-major (NULL: identity), cam_t [N, 3] (NULL: zeros), focal, princpt [N, 2], gender [N] uint8 (NULL: all 0),
+ * given_cam [N, Jr, 3] and given_img [N, Jr, 2] (NULL, or Jr = 0: skipped).  idx [B]: int32, or int64 with idx_is_int64, device
+ * memory.  root_template [G, 3] and root_shapedirs [G, 3, nb]: the rest position and the shape directions of chain joint 0
+ * (the root) of each of the G models, i.e. row 0 of the regressor folded into the template and the shape directions.
+ * Per sample b with row r = idx[b]; ALL arithmetic in float64, each output rounded to fp32 once:
+ *   betas_out   the row; with beta_reset all zeros when any |beta_k| > beta_limit (Human36M :264, which resets a shape with an
+ *               entry beyond 3 to the mean shape).  A NaN compares false and is kept, as there.
+ *   pose_out    the row; with rotate_root its first three values become the PRINCIPAL LOGARITHM of R . exp(root) (:267-273).
+ *               exp is the exact Rodrigues formula of axangle2mat(root / |root|, |root|): with (x, y, z) the unit axis, c, s
+ *               the cosine and sine, C = 1 - c: [[x x C + c, x y C - z s, z x C + y s], [x y C + z s, y y C + c, y z C - x s],
+ *               [z x C - y s, y z C + x s, z z C + c]].  log goes through the quaternion of the product M: of tr M, M00, M11,
+ *               M22 the largest picks Shepperd's branch (ties: in that order), e.g. s = 2 sqrt(1 + tr), w = s / 4, (x, y, z)
+ *               = (M21 - M12, M02 - M20, M10 - M01) / s; the sign is flipped to w >= 0; rotvec = 2 atan2(|v|, w) v / |v|, and
+ *               zero when |v| = 0.  The quaternion is not normalised: atan2 does not need it, so an R that is a rotation only
+ *               to fp32 rounding is taken as it is.  mat2axangle returns the same vector for every angle below pi; at
+ *               exactly pi the sign of the axis is undefined in both.
+ *               DELIBERATE DIFFERENCE: a zero root pose is the identity rotation here (pose_out = log R).  The reference
+ *               divides 0 / 0 (root_pose / angle) and hands NaNs to the body model.
+ *   trans_out   R trans + t_scale cam_t, and with compensate_root + R J0 - J0, where J0 = root_template[g] + root_shapedirs[g]
+ *               . betas_out (the betas AFTER the reset) and g the sample's gender: Human36M :286-291 with t_scale = 1 / 1000;
+ *               AMASS / FreiHAND: trans NULL, t_scale = 1, no compensation.  DELIBERATE DIFFERENCE: the reference subtracts
+ *               the root joint its layer returned in fp32; J0 is the rest root from tables folded in float64 and stored in
+ *               fp32 - the two differ by fp32 rounding of a metre-sized value.
+ *   focal_out, princpt_out, given_cam_out, given_img_out: the rows, bit for bit.  gender_out [B] int32: the row's gender.
+ *   status [B] int32   bit 0: idx outside [0, N) - every output of the sample is zero, gender_out 0, and NO table is read at
+ *               that index;  bit 1: gender >= G - model 0's root is used and gender_out = 0;  bit 2: the beta reset fired;
+ *               bit 3: a non-finite value among the three root values or (cam_R given) R - with rotate_root the root is
+ *               then copied through unchanged; trans_out is what the arithmetic gives.
+ * Errors (P2M_ERR_INVALID, nothing launched): NULL pose, focal, princpt, idx, betas with nb > 0, or a required output
+ * (given_*_out where given_* is read); B < 1 or N < 1; J outside [1, 64], nb outside [0, 64], G outside [1, 4], Jr outside [0,
+ * 32]; compensate_root without the root tables; a NaN scalar; misaligned buffers (4 bytes; an int64 idx: 8).
+ *
+ * p2m_body_select: out[b] = src[gender[b]][b] for verts [B, V, 3], joints [B, NJ, 3] and (JX > 0) extra [B, JX, 3] in one
+ * launch - the choice between the results of G forwards of p2m_body_forward over the same batch.  verts_src, joints_src and
+ * extra_src are HOST arrays of G device pointers.  A gender outside [0, G) counts as 0.  The result is bit for bit the chosen
+ * source.  A streaming copy: 16-byte stores wherever the output's base allows (any 4-byte-aligned base is accepted), 16-byte
+ * loads where the four elements come from one sample's source at an aligned address, else the source is chosen per element.
+ * Errors (P2M_ERR_INVALID, nothing launched): NULL required pointers, G outside [1, 4], B, V or NJ < 1, an output of 2^31
+ * floats or more, misaligned buffers, an output that overlaps a source. */
+int p2m_annot_gather(const float* pose, const float* betas, const float* trans, const float* cam_R, const float* cam_t,
+                     const float* focal, const float* princpt, const uint8_t* gender, const float* given_cam,
+                     const float* given_img, int64_t N, int32_t J, int32_t nb, int32_t Jr, const void* idx,
+                     int32_t idx_is_int64, int32_t B, const float* root_template, const float* root_shapedirs, int32_t G,
+                     int32_t rotate_root, int32_t beta_reset, int32_t compensate_root, double beta_limit, double t_scale,
+                     float* pose_out, float* betas_out, float* trans_out, float* focal_out, float* princpt_out,
+                     int32_t* gender_out, float* given_cam_out, float* given_img_out, int32_t* status, void* stream);
+int p2m_body_select(const float* const* verts_src, const float* const* joints_src, const float* const* extra_src, int32_t G,
+                    const int32_t* gender, int32_t B, int32_t V, int32_t NJ, int32_t JX, float* verts, float* joints,
+                    float* extra, void* stream);
+
 /* ---- Rendering: batched z-buffer rasteriser and image overlay (csrc/render.hip) ------------------------------------------
  * The device counterpart of demo/renderer.py + demo/run.py:46-67 (trimesh, pyrender, OpenGL / EGL, host compositing).  That
  * code needs an OpenGL context and cannot run where this library is built and tested, so this comment is the contract and

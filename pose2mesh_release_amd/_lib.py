@@ -134,6 +134,9 @@ HIP_SYMBOLS = {
     "p2m_train_sample": (_c.c_int, [_vp, _vp, _f32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp,
                                     _i32, _i32, _vp, _vp, _f32, _vp, _vp, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32,
                                     _f32, _f32, _vp, _vp, _i64] + [_vp] * 12),
+    "p2m_annot_gather": (_c.c_int, [_vp] * 10 + [_i64, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32,
+                                    _f64, _f64] + [_vp] * 10),
+    "p2m_body_select": (_c.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "p2m_mesh_project": (_c.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "p2m_mesh_render_workspace": (_c.c_int, [_i32, _i32, _i32, _i32, _i32, _c.POINTER(_i64)]),
     "p2m_mesh_render": (_c.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _i32, _vp, _i32, _i32, _i32, _i32,

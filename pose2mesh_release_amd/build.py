@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 HIP_SOURCES = ["capi.hip", "basis.hip", "gemm.hip", "bn.hip", "optim.hip", "loss.hip", "chebtile.hip", "posenet.hip",
                "eval.hip", "body.hip", "body_bwd.hip", "fscore.hip", "sample.hip", "render.hip", "camfit.hip", "video.hip",
-               "overlay.hip"]
+               "overlay.hip", "annot.hip"]
 # per-source flags.  chebtile.hip: the gather's fmaf chains must stay scalar v_fma_f32 - SLP-packed v_pk_fma_f32 next to the
 # MFMA waves measured 9 % slower over the real-row shapes of a train step (17.2 vs 19.0 ms)
 # fscore.hip: the search loop is 6.5 plain f32 instructions per pair (3 v_sub, v_mul, 2 v_fmac, half a v_min3); SLP-packed it
