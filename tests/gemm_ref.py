@@ -311,6 +311,14 @@ FLAT_TN_CASES = [(r, -(-r // 32) * 32, (32, 32, 64)[i % 3], (1, 3, 3)[i % 3], GR
 # p2m_gemm_tn_acc: (M, Ka, N) - both tile widths
 TN_ACC_CASES = [(M, Ka, N) for M in (32, 36, 100) for Ka, N in ((32, 64), (96, 128), (192, 32))]
 
+# The contractions in PoseNet's role (pose2mesh_release_amd/posenet.py), where the BATCH is a tile dimension; the batches are
+# those of tests/posenet_ref.py's stage cases.  Tables of their own: the ones above are read by the CPU mutation check.
+# dW: p2m_gemm_tn_acc reduces the whole batch in one chunk: (M, Ka, N) - M = 128 .. 516 rows: 8 .. 33 stages of 16, 4 .. 17 of 32
+PN_TN_ACC_CASES = [(M, Ka, N) for M in (128, 132, 260, 516) for Ka, N in ((32, 64), (96, 128))]
+# forward and dX: p2m_gemm_tn with the batch as Ka, the rows of P - no multiple of 32, below, just past one and just past two
+# K tiles of TILE rows: (M, chunk_rows, Ka, planes, gplanes, Gc, a0_shift), M = 256 reduced in 4 chunks of 64
+PN_TN_CASES = [(256, 64, Ka, 1, 1, Gc, 0) for Ka in (36, 132, 260) for Gc in (64, 128)]
+
 
 # ---- inputs (seeded, on the CPU: the GPU test and the mutation check use the same tensors) ------------------------------------
 

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 import torch
 
+import posenet_ref as pnr
 import tile_plan_ref as tp
 
 pytestmark = pytest.mark.gpu
@@ -1066,9 +1067,8 @@ def test_graph_conv_cheby_outliers(ops, monkeypatch, where, spot, Fin, Fout):
 
 # ---- 6. the PoseNet stages directly ------------------------------------------------------------------------------------------
 
-# (bias, residual, BatchNorm: None / "train" / "eval", p_drop)
-PN_VARIANTS = [(True, True, "train", 0.5), (True, False, "eval", 0.0), (False, True, "train", 0.0), (True, True, None, 0.0),
-               (False, False, "eval", 0.5)]
+# (bias, residual, BatchNorm: None / "train" / "eval", p_drop); the float64 restatement of a stage is tests/posenet_ref.py
+PN_VARIANTS = pnr.PN_VARIANTS
 PN_SHAPES = [(32, 0, 32), (36, 33, 68), (64, 64, 4096)]
 # input seeds: of the 262 144 elements of the widest case 1 - 2 per BatchNorm variant lie within 1e-5 of the ReLU kink on an
 # average draw; with these seeds none does in any variant (counted in float64 on the host)
@@ -1076,13 +1076,7 @@ PN_SEEDS = {(64, 4096, 1): 11, (64, 4096, 3): 169}
 
 
 def _pn_inputs(B, Br, F, nch, seed):
-    gen = torch.Generator().manual_seed(seed)
-    d = {"P": torch.randn(nch, B, F, generator=gen), "bias": torch.randn(F, generator=gen),
-         "resid": torch.randn(B, F, generator=gen), "rnd": torch.rand(B, F, generator=gen),
-         "gamma": torch.rand(F, generator=gen) + 0.5, "beta": 0.2 * torch.randn(F, generator=gen),
-         "rm": 0.1 * torch.randn(F, generator=gen), "rv": torch.rand(F, generator=gen) + 0.5,
-         "G": torch.randn(nch, B, F, generator=gen), "addend": torch.randn(B, F, generator=gen)}
-    d = {k: v.cuda() for k, v in d.items()}
+    d = {k: v.cuda() for k, v in pnr.pn_inputs(B, F, nch, seed).items()}
     pad = torch.arange(Br, B, device="cuda")
     return d, pad
 
@@ -1126,29 +1120,19 @@ def test_pn_stage_fwd(ops, monkeypatch, B, B_real, F, nch):
         assert (a[Br:] == 0).all() and (aT[:, Br:] == 0).all()
         assert torch.equal(z[:Br], z0[:Br])
         # float64
-        zd = d["P"].double().sum(0)[:Br]
-        if bias:
-            zd = zd + d["bias"].double()
-        if resid:
-            zd = zd + d["resid"].double()[:Br]
+        zd = pnr.z_ref(d["P"], Br, d["bias"] if bias else None, d["resid"] if resid else None)
         _chk("z", (z[:Br].double() - zd).abs().max(), 1e-5)
-        if bn is None:
-            ad = zd
-        else:
+        ad, _, mu, var, istd = pnr.act_ref(zd, bn, d["gamma"], d["beta"], d["rm"], d["rv"], d["rnd"], p_drop)
+        if bn is not None:
             assert torch.equal(mean, mean0) and torch.equal(invstd, invstd0) and torch.equal(rm, rm0) and torch.equal(rv, rv0)
             if bn == "train":
-                mu, var = zd.mean(0), zd.var(0, unbiased=False)
-                _chk("running_mean", (rm.double() - (0.9 * d["rm"].double() + 0.1 * mu)).abs().max(), 1e-5)
-                _chk("running_var", (rv.double() - (0.9 * d["rv"].double() + 0.1 * var * Br / (Br - 1))).abs().max(), 1e-5)
+                rmd, rvd = pnr.running_ref(d["rm"], d["rv"], mu, var, Br)
+                _chk("running_mean", (rm.double() - rmd).abs().max(), 1e-5)
+                _chk("running_var", (rv.double() - rvd).abs().max(), 1e-5)
             else:
-                mu, var = d["rm"].double(), d["rv"].double()
                 assert torch.equal(rm, d["rm"]) and torch.equal(rv, d["rv"])
-            istd = 1.0 / torch.sqrt(var + 1e-5)
             _chk("mean", (mean.double() - mu).abs().max(), 1e-5)
             _chk("invstd", (invstd.double() - istd).abs().max(), 1e-5)
-            ad = torch.relu((zd - mu) * istd * d["gamma"].double() + d["beta"].double())
-            if p_drop > 0:
-                ad = torch.where(d["rnd"][:Br] >= p_drop, ad / (1.0 - p_drop), torch.zeros_like(ad))
         _chk("a", (a[:Br].double() - ad).abs().max(), 1e-5)
         # the maximum planted at row B_real - 1, last column, and at row 0, column 0 (the column's gamma raised so that the
         # batch normalisation, which caps an outlier at sqrt(B - 1), cannot hide it; its dropout draw set to `keep`)
@@ -1213,25 +1197,10 @@ def test_pn_stage_bwd(ops, monkeypatch, B, B_real, F, nch):
             return gz, gzT, dg, db, dbias
 
         d["z"] = z
-        # float64 autograd on the saved z
-        zd = z[:Br].double().requires_grad_(True)
-        gam, bet = d["gamma"].double().requires_grad_(True), d["beta"].double().requires_grad_(True)
-        ga = d["G"].double().sum(0)[:Br]
-        near = torch.zeros_like(ga, dtype=torch.bool)
-        if bn is None:
-            ad = zd
-        else:
-            if bn == "train":
-                mu, var = zd.mean(0), zd.var(0, unbiased=False)
-            else:
-                mu, var = d["rm"].double(), d["rv"].double()
-            pre = (zd - mu) / torch.sqrt(var + 1e-5) * gam + bet
-            near = pre.detach().abs() < 1e-5
-            ad = torch.relu(pre)
-            if p_drop > 0:
-                ad = torch.where(d["rnd"][:Br] >= p_drop, ad / (1.0 - p_drop), torch.zeros_like(ad))
-        (ad * ga).sum().backward()
-        gzd = zd.grad + (d["addend"].double()[:Br] if resid else 0.0)
+        # float64 on the saved z: the closed-form backward of tests/posenet_ref.py, which tests/test_posenet_ref_cpu.py holds
+        # to torch's float64 autograd of the same lines within 1e-12
+        gzd, dgd, dbd, rb, near = pnr.bwd_ref(z[:Br], d["G"].double().sum(0)[:Br], bn, d["gamma"], d["beta"], d["rm"], d["rv"],
+                                              d["rnd"], p_drop, d["addend"] if resid else None)
         print(f"    {int(near.sum())} elements within 1e-5 of the ReLU kink")
         assert int(near.sum()) <= 2
         for accumulate in (False, True):
@@ -1247,10 +1216,9 @@ def test_pn_stage_bwd(ops, monkeypatch, B, B_real, F, nch):
             base = 1.5 if accumulate else 0.0
             diff = torch.where(near, torch.zeros_like(gzd), gz[:Br].double() - gzd)
             _chk("gz", diff.abs().max(), 2e-5 * max(1.0, float(gzd.abs().max())))
-            rb = gzd.sum(0)
             _chk("dbias", (dbias.double() - base - rb).abs().max(), 1e-5 * np.sqrt(B) * max(1.0, float(rb.abs().max())))
             if bn is not None:
-                for nm, gotp, ref in (("dgamma", dg, gam.grad), ("dbeta", db, bet.grad)):
+                for nm, gotp, ref in (("dgamma", dg, dgd), ("dbeta", db, dbd)):
                     _chk(nm, (gotp.double() - base - ref).abs().max(), 1e-5 * np.sqrt(B) * max(1.0, float(ref.abs().max())))
         # the maximum of gz planted at row B_real - 1, last column, and at row 0, column 0: the incoming gradient there is 50 and
         # the element is made active (z one standard deviation above the saved mean, gamma 1, beta 0.1, dropout draw `keep`)

@@ -358,3 +358,50 @@ def test_gemm_tn_acc(arith, hip_libs):
         torch.cuda.synchronize()
         worst.chk("P", what, ((P.double() - 0.25) - ref).abs().max(), gr.tol_grad(ref, M))
     worst.done()
+
+
+# ---- the contractions in PoseNet's role: the batch as a tile dimension ---------------------------------------------------------
+
+def test_gemm_tn_acc_posenet_batches(arith, hip_libs):
+    """p2m_gemm_tn_acc as PoseNet's dW (pose2mesh_release_amd/posenet.py: dW += g_z^T a): the WHOLE batch reduced in one chunk,
+    M in {128, 132, 260, 516} rows - 8 .. 33 stages of 16 rows (4 .. 17 of 32 in f32), with a 4-row tail at 132, 260 and 516 -
+    at both tile widths; P prefilled with 0.25."""
+    worst = _Worst(f"gemm_tn_acc (PoseNet batches) {arith}")
+    for index, (M, Ka, N) in enumerate(gr.PN_TN_ACC_CASES):
+        what = f"case {index}: M {M}, Ka {Ka}, N {N}"
+        gen = torch.Generator().manual_seed(6000 + index)
+        A, G = torch.randn(M, Ka, generator=gen).cuda(), torch.randn(M, N, generator=gen).cuda()
+        P = torch.full((Ka, N), 0.25, device="cuda")
+        ref = gr.gemm_tn_acc_ref(A, G, P) - 0.25
+        _ck(_hip().p2m_gemm_tn_acc(_vp(A), Ka, _vp(G), N, M, _vp(P), CODE[arith], _vp(_word(arith, A)), _vp(_word(arith, G)),
+                                   _st()), "p2m_gemm_tn_acc")
+        torch.cuda.synchronize()
+        worst.chk("P", what, ((P.double() - 0.25) - ref).abs().max(), gr.tol_grad(ref, M))
+    worst.done()
+
+
+def test_gemm_tn_posenet_batches(arith, hip_libs):
+    """p2m_gemm_tn as PoseNet's forward and dX, where the batch is Ka - the ROWS of P: Ka in {36, 132, 260}, no multiple of 32,
+    below, 4 rows past one and 4 rows past two K tiles of p2m_stats_tile_rows() rows; one A plane, one G plane of 64 or 128
+    columns, M = 256 reduced in 4 chunks of 64.  P and Pdb lie in sentinel-filled buffers and are wholly written; per chunk and
+    summed over the chunks (what the stage kernels then add up) against float64."""
+    assert int(_hip().p2m_stats_tile_rows()) == gr.TILE
+    assert [(Ka % 32 != 0, -(-Ka // gr.TILE), Ka % gr.TILE) for Ka in sorted({c[2] for c in gr.PN_TN_CASES})] == \
+        [(True, 1, 36), (True, 2, 4), (True, 3, 4)]
+    worst = _Worst(f"gemm_tn (PoseNet batches) {arith}")
+    for index, (M, cr, Ka, pl, gpl, Gc, sh) in enumerate(gr.PN_TN_CASES):
+        what = f"case {index}: M {M}, chunk_rows {cr}, Ka {Ka} x {pl}, G {gpl} x {Gc}, shift {sh}"
+        print("  " + what)
+        gen = torch.Generator().manual_seed(7000 + index)
+        A = [torch.randn((M + 1) >> sh if q == 0 else M, Ka, generator=gen).cuda() for q in range(pl)]
+        G = [torch.randn(M, Gc, generator=gen).cuda() for _ in range(gpl)]
+        Pref, Pdbref, nrows = gr.gemm_tn_ref(A, sh, G, M, cr)
+        assert nrows == [64] * 4
+        P, Pdb = _tn_flat(arith, A, Ka, sh, G, Gc, M, cr, len(nrows))
+        assert not (_bits(P) == SENTINEL).any() and not (_bits(Pdb) == SENTINEL).any(), what
+        for c, r in enumerate(nrows):
+            worst.chk("P", f"{what}, chunk {c} ({r} rows)", (P[c].double() - Pref[c]).abs().max(), gr.tol_grad(Pref[c], r))
+            worst.chk("Pdb", f"{what}, chunk {c} ({r} rows)", (Pdb[c].double() - Pdbref[c]).abs().max(), gr.tol_pdb(r))
+        worst.chk("P", f"{what}, summed", (P.double().sum(0) - Pref.sum(0)).abs().max(), gr.tol_grad(Pref.sum(0), M))
+        worst.chk("Pdb", f"{what}, summed", (Pdb.double().sum(0) - Pdbref.sum(0)).abs().max(), gr.tol_pdb(M))
+    worst.done()
