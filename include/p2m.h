@@ -693,6 +693,7 @@ int p2m_body_backward(const float* pose, const float* pose_mean, const float* be
  *   8 table       block 0: word 0 the Bernoulli uniform, words 1, 2 the Box-Muller pair (u0, u1)
  *   9 augment     joint 0, block 0: word 0 flip, words 1, 2 the rotation's Box-Muller pair, word 3 rot = 0 (p2m_train_sample)
  *  10 camera start   joint 0, block 0: words 0, 1, 2 the start (s, tx, ty) of the camera fit (p2m_camera_fit)
+ *  11 person colour  joint 0, block 0: word 0 the hue of a person's colour (p2m_person_colours)
  * with ks_q = sqrt(area) 2 sigma_j sqrt(-2 ln q) (get_dist_wrt_ks, lib/noise_utils.py:18-24; a negative or NaN area counts
  * as 0).  tests/sample_ref.py mirrors all of this in numpy, float64.
  *
@@ -1086,6 +1087,64 @@ int p2m_pose_overlay(const float* poses, int32_t B, int32_t P, int32_t J, int32_
                      const uint8_t* colours, int32_t colour_mode, const float* boxes, uint32_t box_rgb, const uint8_t* src,
                      uint8_t* dst, int32_t H, int32_t W, float thr, int32_t line_h2, int32_t mark_h2, int32_t mark_r16,
                      int32_t box_h2, int32_t alpha256, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- The crowd demo's front end: who is in the picture, and their colours (csrc/crowd.hip) -----------------------------------
+ * The head of the crowd branch of demo/run.py: add_pelvis / add_neck (:127-146), the score filter and the greedy suppression
+ * of duplicate detections (:276-306), and one random colour per accepted person (:314).  One launch each on `stream`, no
+ * allocation, no synchronisation (capturable).  tests/crowd_ref.py restates both in numpy, float64.
+ *
+ * p2m_crowd_select: dets fp32 [B, P, J, 3] = (x, y, confidence) of up to P detections per image in the detector's list order;
+ *   num int32 [B] on the device or NULL: how many of the P slots of image b are filled (clamped to [0, P]; NULL: all P).  A slot
+ *   at or beyond num[b] is never read.  midpoints: HOST array [n_mid, 2] of input-joint indices in [0, J), n_mid in [0, 8],
+ *   Jo = J + n_mid <= 64, P in [1, 64].  pose_thr, score_thr, min_diff: the reference's 0.1, 1.5, 20.
+ *   One block per image.  ALL DECISION ARITHMETIC IS FLOAT64 on the fp32 inputs widened exactly, every operation rounded once
+ *   and none fused (this unit is built with -ffp-contract=off).  Per image, with i, d slots and j < Jo joints:
+ *     midpoints  joint J + m = midpoint m of (a, b):  xy = (xy_a + xy_b) * 0.5,  conf = conf_a * conf_b  (the product)
+ *     valid      valid_ij = conf_ij > pose_thr  (strict; over all Jo joints)
+ *     score      score_i = ((conf_i0 + conf_i1) + conf_i2) + .. + conf_i,Jo-1: sequential, in index order (Python's sum)
+ *     non-finite a slot with a NaN or an infinity among the x, y, confidence of its J INPUT joints: reason 3.  This rule is this
+ *                project's: in the reference such a detection poisons the mean of every later comparison.  Here it is dropped,
+ *                never enters the accepted list and so suppresses nobody.
+ *     low score  score_i < score_thr (strict): reason 1; never enters the accepted list.
+ *     duplicate(i, d), d an ACCEPTED slot before i:  the terms t = |v_i - v_d| for v = x_j, y_j of every joint j with valid_ij
+ *                and valid_dj, walked JOINT-MAJOR, x BEFORE y (j = 0: x, y; j = 1: x, y; ..); a term equal to 0 is left out (two
+ *                coinciding coordinates do not count, as a masked joint does not: the reference's diff[diff != 0]);
+ *                S = sum of the kept terms, added sequentially in that order, n = their number;
+ *                n == 0: a duplicate;  otherwise mean = S / n (one correctly rounded division) and a duplicate iff
+ *                mean < min_diff (strict).
+ *     greedy     slots are visited in list order; slot i with reason 0 so far is compared with every slot accepted before it
+ *                and ONLY those: a duplicate of any of them gets reason 2 and dup_of = the lowest such slot; otherwise it is
+ *                accepted (reason 0).  A slot suppressed by an accepted one suppresses nobody itself.
+ *   The pair tests are independent and spread over the block's waves (a 64-bit mask of matching earlier slots per slot, built
+ *   by ballots: no atomics), the greedy scan over the masks is serial on one wave, the compaction a popcount of the accepted
+ *   mask below each bit.  An image's outputs depend on that image alone and are reproducible bit for bit.
+ *   Outputs:  joints fp32 [B, P, Jo, 3]: the accepted slots of each image compacted to the front in list order, (x, y, conf)
+ *             with the midpoints rounded ONCE from float64 to fp32; every remaining slot is filled with quiet NaNs (7FC00000):
+ *             p2m_pose_prepare zeroes such a sample (status bit 0), p2m_camera_fit returns cam = 0 for it, the rasteriser
+ *             skips its faces, p2m_pose_overlay draws nothing of it - an absent person needs no host round trip
+ *             count int32 [B];  index int32 [B, P]: the input slot of compacted person k, -1 for k >= count
+ *             per INPUT slot: reason int8 [B, P] (0 accepted, 1 low score, 2 duplicate, 3 non-finite, -1 at or beyond num),
+ *             dup_of int32 [B, P] (-1 unless reason 2), score fp64 [B, P] (the quiet NaN 7FF8000000000000 for reasons 3 and
+ *             -1), keep uint8 [B, P] = (reason == 0)
+ *   Errors (P2M_ERR_INVALID, nothing launched): a NULL required pointer (everything but num; midpoints when n_mid > 0), B
+ *   outside [1, 2^24], P outside [1, 64], J < 1, n_mid outside [0, 8], Jo > 64, a midpoint index outside [0, J), a threshold
+ *   that is not finite, score not 8-byte aligned.
+ *
+ * p2m_person_colours: n colours, colorsys.hsv_to_rgb(h_k, s, v) with the hue drawn from the project's one Philox stream
+ *   ("training-sample noise" above) as
+ *     stage 11 "person colour", joint 0, block 0: h = (word 0 >> 8) 2^-24, counter = the global index state[1] + k
+ *   (stages 0-10 are untouched; the caller advances state[1] by n with a tensor add, as for p2m_camera_fit).  Float64, every
+ *   operation rounded once:  s == 0: (v, v, v);  otherwise i = (int)(6 h), f = 6 h - i, p = v (1 - s), q = v (1 - s f),
+ *   t = v (1 - s (1 - f)), and by i mod 6:  0 (v, t, p)  1 (q, v, p)  2 (p, v, t)  3 (p, q, v)  4 (t, p, v)  5 (v, p, q).
+ *   rgb fp32 [n, 3]: each channel rounded once to fp32 (what p2m_mesh_render's colours take);  u8 uint8 [n, 3]: 255 times the
+ *   FLOAT64 channel, rounded half to even (what p2m_pose_overlay's per-person colours take; the same channel order - nothing
+ *   here swaps channels).  Either output may be NULL, not both.
+ *   Errors (P2M_ERR_INVALID, nothing launched): NULL or misaligned (8 bytes) state, both outputs NULL, n outside [1, 2^24], s or
+ *   v outside [0, 1] or not finite.                                                                                          */
+int p2m_crowd_select(const float* dets, const int32_t* num, int32_t B, int32_t P, int32_t J, const int32_t* midpoints,
+                     int32_t n_mid, double pose_thr, double score_thr, double min_diff, float* joints, int32_t* count,
+                     int32_t* index, int8_t* reason, int32_t* dup_of, double* score, uint8_t* keep, void* stream);
+int p2m_person_colours(const uint64_t* state, int32_t n, double s, double v, float* rgb, uint8_t* u8, void* stream);
 
 #ifdef __cplusplus
 }

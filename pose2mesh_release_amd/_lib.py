@@ -150,6 +150,9 @@ HIP_SYMBOLS = {
     "p2m_pose_overlay_workspace": (_c.c_int, [_i32, _i32, _i32, _i32, _c.POINTER(_i64)]),
     "p2m_pose_overlay": (_c.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _c.c_uint32, _vp, _vp, _i32, _i32,
                                     _f32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp]),
+    "p2m_crowd_select": (_c.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _vp]),
+    "p2m_person_colours": (_c.c_int, [_vp, _i32, _f64, _f64, _vp, _vp, _vp]),
 }
 
 HOST_SYMBOLS = {

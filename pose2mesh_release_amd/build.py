@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 HIP_SOURCES = ["capi.hip", "basis.hip", "gemm.hip", "bn.hip", "optim.hip", "loss.hip", "chebtile.hip", "posenet.hip",
                "eval.hip", "body.hip", "body_bwd.hip", "fscore.hip", "sample.hip", "render.hip", "camfit.hip", "video.hip",
-               "overlay.hip", "annot.hip"]
+               "overlay.hip", "annot.hip", "crowd.hip"]
 # per-source flags.  chebtile.hip: the gather's fmaf chains must stay scalar v_fma_f32 - SLP-packed v_pk_fma_f32 next to the
 # MFMA waves measured 9 % slower over the real-row shapes of a train step (17.2 vs 19.0 ms)
 # fscore.hip: the search loop is 6.5 plain f32 instructions per pair (3 v_sub, v_mul, 2 v_fmac, half a v_min3); SLP-packed it
@@ -26,8 +26,11 @@ HIP_SOURCES = ["capi.hip", "basis.hip", "gemm.hip", "bn.hip", "optim.hip", "loss
 # change the bits the float64 yardstick (tests/camfit_ref.py) is compared with step by step
 # video.hip: the same contract for the One-Euro filter, whose output is pinned bit for bit to the reference's float32 numpy
 # arithmetic (tests/video_ref.py)
+# crowd.hip: the same contract for the crowd filter's float64 decisions (midpoints, masked means) and the colour formula, which
+# are compared exactly with tests/crowd_ref.py
 HIP_SOURCE_FLAGS = {"chebtile.hip": ["-fno-slp-vectorize"], "fscore.hip": ["-fno-slp-vectorize"],
-                    "camfit.hip": ["-ffp-contract=off"], "video.hip": ["-ffp-contract=off"]}
+                    "camfit.hip": ["-ffp-contract=off"], "video.hip": ["-ffp-contract=off"],
+                    "crowd.hip": ["-ffp-contract=off"]}
 HIP_HEADERS = ["p2m_common.h", "p2m_body.h", "p2m_split.h", "p2m_eval.h", "p2m_philox.h", os.path.join("..", "..", "include", "p2m.h")]
 HIP_LIB = os.path.join(LIBDIR, "libp2m_hip.so")
 HOST_LIB = os.path.join(LIBDIR, "libp2m_host.so")
