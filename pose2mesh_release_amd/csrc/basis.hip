@@ -385,6 +385,121 @@ __global__ __launch_bounds__(256) void k_expand_small_tile(TilePlan pl, const in
   for (int c = 3 * NC; c < lde; c++) e[c] = 0.f;
 }
 
+// ---- the two expand kernels with E written as whole rows (NC = 3, lde % 4 == 0, E 16-byte aligned; P2M_NARROW_ROWS) --------
+// Same entry order and t1 / t2 chains as above.  The 9 values of a row go to LDS as three float4 {G | t1 | t2 | 0 0 0}, and
+// lde / 4 neighbouring lanes then store one E row each as 16-byte units, zero tail included: a store instruction covers
+// 1 KB of whole rows where a thread's scalar stores touched 64 rows with 4 bytes each.
+constexpr int EXP_NC = 3, EXP_Q = 3;       // float4 units that hold data in a row
+
+__device__ __forceinline__ void expand_stage_row(float4* r, const float* g, const float* t1, const float* t2) {
+  r[0] = make_float4(g[0], g[1], g[2], t1[0]);
+  r[1] = make_float4(t1[1], t1[2], t2[0], t2[1]);
+  r[2] = make_float4(t2[2], 0.f, 0.f, 0.f);
+}
+
+// rows of the block -> E; erow[i] = the row's index in E (in lde-float rows), < 0: not written
+__device__ __forceinline__ void expand_copy_out(const float4* res, const long* erow, int nrows, float* __restrict__ E, int lde) {
+  const int L4 = lde >> 2;
+  for (int u = threadIdx.x; u < nrows * L4; u += 256) {
+    const int i = u / L4, q = u - i * L4;
+    const long er = erow[i];
+    if (er < 0) continue;
+    const float4 v = q < EXP_Q ? res[i * EXP_Q + q] : make_float4(0.f, 0.f, 0.f, 0.f);
+    reinterpret_cast<float4*>(E + er * lde)[q] = v;
+  }
+}
+
+// under classes (g.w != nullptr) the holes are not written: E is read through row sets 1 and 2 only (real_ids and the
+// representatives in fake_ids, row_set_of), as every other tensor with holes
+__global__ __launch_bounds__(256) void k_expand_small_rows(Graph g, const float* __restrict__ G, float* __restrict__ E,
+                                                            int lde, int B, int skip_real) {
+  __shared__ float4 res[256 * EXP_Q];
+  __shared__ long erow[256];
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  long er = -1;
+  if (idx < (long)B * g.V) {
+    const int row = (int)(idx % g.V);
+    const int j0 = g.rowptr[row], j1 = g.rowptr[row + 1];
+    const bool live = !(skip_real && j1 - j0 > 1) && !(g.w != nullptr && g.w[row] == 0.f);
+    if (live) {
+      const long base = (idx - row) * EXP_NC;
+      float t1[EXP_NC], t2[EXP_NC], gv[EXP_NC];
+#pragma unroll
+      for (int c = 0; c < EXP_NC; c++) t1[c] = t2[c] = 0.f;
+      for (int j = j0; j < j1; j++) {
+        const float* q = G + base + (long)g.col[j] * EXP_NC;
+        const float a = g.a[j], b = g.b[j];
+#pragma unroll
+        for (int c = 0; c < EXP_NC; c++) {
+          t1[c] = fmaf(a, q[c], t1[c]);
+          t2[c] = fmaf(b, q[c], t2[c]);
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < EXP_NC; c++) gv[c] = G[idx * EXP_NC + c];
+      expand_stage_row(res + threadIdx.x * EXP_Q, gv, t1, t2);
+      er = idx;
+    }
+  }
+  erow[threadIdx.x] = er;
+  __syncthreads();
+  expand_copy_out(res, erow, 256, E, lde);
+}
+
+__global__ __launch_bounds__(256) void k_expand_small_tile_rows(TilePlan pl, const int* __restrict__ real_ids, int V,
+                                                                 const float* __restrict__ G, float* __restrict__ E, int lde,
+                                                                 int B) {
+  __shared__ float4 ents[TILE_ECAP];
+  __shared__ int rowoff[TILE_RMAX + 1];
+  __shared__ float xs[SMALL_SPB][TILE_UCAP][EXP_NC];
+  __shared__ float4 res[256 * EXP_Q];
+  __shared__ long erow[256];
+  // (logical block order: the tiles of a sample group are neighbours and read the same rows of G - one L2 fetches them, not
+  //  eight)
+  const int bid = xcd_block_id(blockIdx.x, gridDim.x);
+  const int tile = bid % pl.ntiles, sg = bid / pl.ntiles;
+  const int t = threadIdx.x;
+  const int r0 = pl.tile_row[tile], R = pl.tile_row[tile + 1] - r0;
+  const int u0 = pl.tile_u[tile], U = pl.tile_u[tile + 1] - u0;
+  const int e0 = pl.erow[r0], nE = pl.erow[r0 + R] - e0;
+  for (int i = t; i < nE; i += 256) ents[i] = pl.ent[e0 + i];
+  if (t <= R) rowoff[t] = pl.erow[r0 + t] - e0;
+  const int b0 = sg * SMALL_SPB;
+  for (int q = t; q < U * SMALL_SPB; q += 256) {
+    const int u = q % U, sl = q / U, b = b0 + sl;
+    if (b < B) {
+      const float* src = G + ((long)b * V + pl.ucol[u0 + u]) * EXP_NC;
+#pragma unroll
+      for (int c = 0; c < EXP_NC; c++) xs[sl][u][c] = src[c];
+    }
+  }
+  __syncthreads();
+  const int i = t % TILE_RMAX, sl = t / TILE_RMAX, b = b0 + sl;
+  long er = -1;
+  if (i < R && b < B) {
+    const long ridx = (long)b * V + real_ids[r0 + i];
+    float t1[EXP_NC], t2[EXP_NC], gv[EXP_NC];
+#pragma unroll
+    for (int c = 0; c < EXP_NC; c++) t1[c] = t2[c] = 0.f;
+    for (int j = rowoff[i]; j < rowoff[i + 1]; j++) {
+      const float4 en = ents[j];
+      const float* q = xs[sl][__float_as_int(en.z)];
+#pragma unroll
+      for (int c = 0; c < EXP_NC; c++) {
+        t1[c] = fmaf(en.x, q[c], t1[c]);
+        t2[c] = fmaf(en.y, q[c], t2[c]);
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < EXP_NC; c++) gv[c] = G[ridx * EXP_NC + c];
+    expand_stage_row(res + t * EXP_Q, gv, t1, t2);
+    er = ridx;
+  }
+  erow[t] = er;
+  __syncthreads();
+  expand_copy_out(res, erow, 256, E, lde);
+}
+
 }  // namespace p2m
 
 using namespace p2m;
@@ -445,10 +560,20 @@ extern "C" int p2m_cheb_expand_small(p2m_graph_t gh, const float* G, int32_t nc,
   hipStream_t s = (hipStream_t)stream;
   int skip_real = 0;
   const TilePlan& pl = g.plan[0];
+  // whole-row stores (k_expand_small_rows / _tile_rows): nc = 3 and 16-byte rows of E
+  const bool rows16 = nc == 3 && lde % 4 == 0 && (reinterpret_cast<uintptr_t>(E) & 15) == 0 && narrow_rows();
   if (pl.ntiles > 0 && basis_tiled() && nc == 3) {
-    hipLaunchKernelGGL(k_expand_small_tile<3>, dim3(pl.ntiles * cdiv(B, SMALL_SPB)), dim3(256), 0, s, pl, g.real_ids, g.V,
-                       G, E, lde, B);
+    if (rows16)
+      hipLaunchKernelGGL(k_expand_small_tile_rows, dim3(pl.ntiles * cdiv(B, SMALL_SPB)), dim3(256), 0, s, pl, g.real_ids,
+                         g.V, G, E, lde, B);
+    else
+      hipLaunchKernelGGL(k_expand_small_tile<3>, dim3(pl.ntiles * cdiv(B, SMALL_SPB)), dim3(256), 0, s, pl, g.real_ids, g.V,
+                         G, E, lde, B);
     skip_real = 1;
+  }
+  if (rows16) {
+    hipLaunchKernelGGL(k_expand_small_rows, dim3(cdiv(tot, 256)), dim3(256), 0, s, g, G, E, lde, B, skip_real);
+    return check_launch("cheb_expand_small");
   }
   switch (nc) {
     case 1: hipLaunchKernelGGL(k_expand_small<1>, dim3(cdiv(tot, 256)), dim3(256), 0, s, g, G, E, lde, B, skip_real); break;

@@ -442,6 +442,44 @@ __global__ __launch_bounds__(256) void k_class_reduce(const float* __restrict__ 
   out[idx] = s;
 }
 
+// F = 3 (the final conv's gradient): one thread per row and pass, a block = CR3_ROWS consecutive rows = 12 KB contiguous in
+// `in` and in `out`.  The block's rows pass through LDS so that both sides move as whole 16-byte units (in, out 16-byte
+// aligned; the tail of the last block element by element); a thread replaces its own row in LDS by the row's result, a
+// representative adding the other rows of its class from memory in the order k = 0 .. m-1 of the generic kernel.  The class
+// size is read once per row and no index is divided per element.
+constexpr int CR3_ROWS = 1024;
+__global__ __launch_bounds__(256) void k_class_reduce3(const float* __restrict__ in, const float* __restrict__ w,
+                                                        float* __restrict__ out, long M, int V) {
+  __shared__ float4 buf4[CR3_ROWS * 3 / 4];
+  float* buf = reinterpret_cast<float*>(buf4);
+  const int t = threadIdx.x;
+  const long r0 = (long)blockIdx.x * CR3_ROWS;
+  const int rows = (int)(M - r0 < CR3_ROWS ? M - r0 : CR3_ROWS);
+  const int n = rows * 3, n4 = n >> 2;
+  const float* src = in + r0 * 3;
+  float* dst = out + r0 * 3;
+  for (int i = t; i < n4; i += 256) buf4[i] = reinterpret_cast<const float4*>(src)[i];
+  if (t < n - 4 * n4) buf[4 * n4 + t] = src[4 * n4 + t];
+  __syncthreads();
+  const int v0 = (int)(r0 % V);                  // one block-uniform 64-bit division, then 32-bit
+  for (int row = t; row < rows; row += 256) {
+    const int m = (int)w[(v0 + row) % V];
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    if (m > 0) {
+      s0 += buf[3 * row]; s1 += buf[3 * row + 1]; s2 += buf[3 * row + 2];
+      const float* p = src + 3 * row;
+      for (int k = 1; k < m; k++) {
+        p += 3;
+        s0 += p[0]; s1 += p[1]; s2 += p[2];
+      }
+    }
+    buf[3 * row] = s0; buf[3 * row + 1] = s1; buf[3 * row + 2] = s2;
+  }
+  __syncthreads();
+  for (int i = t; i < n4; i += 256) reinterpret_cast<float4*>(dst)[i] = buf4[i];
+  if (t < n - 4 * n4) dst[4 * n4 + t] = buf[4 * n4 + t];
+}
+
 // ---- backward ---------------------------------------------------------------------------------
 // rows per block of the reduction: 512 for the big levels; fewer when that would leave the 256 CUs with a handful of
 // blocks each (F = 256 at V <= 2944: 580-1100 blocks of 512 rows ran at 2.4 TB/s)
@@ -1238,7 +1276,11 @@ extern "C" int p2m_class_reduce(p2m_graph_t gh, const float* in, float* out, int
   P2M_CHECK_ARG(g.w != nullptr, "the handle has no classes (p2m_graph_set_classes)");
   if (B <= 0) return P2M_OK;
   const long M = (long)B * g.V;
-  hipLaunchKernelGGL(k_class_reduce, dim3(cdiv(M * F, 256)), dim3(256), 0, (hipStream_t)stream, in, g.w, out, M, g.V, F);
+  const bool aligned = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  if (F == 3 && aligned && narrow_rows())
+    hipLaunchKernelGGL(k_class_reduce3, dim3(cdiv(M, CR3_ROWS)), dim3(256), 0, (hipStream_t)stream, in, g.w, out, M, g.V);
+  else
+    hipLaunchKernelGGL(k_class_reduce, dim3(cdiv(M * F, 256)), dim3(256), 0, (hipStream_t)stream, in, g.w, out, M, g.V, F);
   return check_launch("class_reduce");
 }
 

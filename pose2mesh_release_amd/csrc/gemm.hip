@@ -2096,6 +2096,154 @@ __global__ __launch_bounds__(256) void k_conv_weights_images(const ConvWeights* 
   });
 }
 
+// ---- the same four images, tiled through LDS (P2M_NARROW_ROWS = 1) -------------------------------------------------------
+// A block takes a 32 (fo) x 32 (fin) tile of W - 32 runs of 96 contiguous floats, read once along W's fast axis - and emits the
+// tile's part of all four images from LDS: an item is 8 consecutive k of one n, i.e. one 16-byte store per slice, and the 64
+// lanes of a wave cover (n, half) pairs that are contiguous in the image (1 KB per slice and store).  The tile grid spans
+// Npad in both directions, so the zero columns n >= N come out of the same stores.  Values, split and trailer word are those
+// of write_weight_image.  An image whose K is not cut into 16-groups along the tile (Fin or Fout not a multiple of 16) or
+// that is not 16-byte aligned is written by write_weight_image.
+constexpr int WI_T = 32;                  // tile edge
+constexpr int WI_LD = 3 * WI_T + 1;       // LDS row: 96 floats + 1 (a column walk then touches 32 different banks)
+
+__device__ __forceinline__ float weight_eff_value(const float* w, float a, float b) { return w[0] + a * w[1] + b * w[2]; }
+
+template <int NS>
+__device__ __forceinline__ void store_k8(unsigned short* __restrict__ dst, long sl, const float (&v)[8], float sc) {
+  unsigned short s[NS][8];
+#pragma unroll
+  for (int e = 0; e < 8; e++) {
+    if constexpr (NS == 3) {
+      unsigned h, m, l;
+      split3(v[e], h, m, l);
+      s[0][e] = (unsigned short)(h >> 16);
+      s[1][e] = (unsigned short)(m >> 16);
+      s[2][e] = (unsigned short)(l >> 16);
+    } else {
+      const float y = v[e] * sc;
+      const _Float16 h = (_Float16)y;
+      const _Float16 l = (_Float16)(y - (float)h);
+      s[0][e] = __builtin_bit_cast(unsigned short, h);
+      s[1][e] = __builtin_bit_cast(unsigned short, l);
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < NS; q++) {
+    u32x4 p;
+#pragma unroll
+    for (int i = 0; i < 4; i++) p[i] = (unsigned)s[q][2 * i] | ((unsigned)s[q][2 * i + 1] << 16);
+    *reinterpret_cast<u32x4*>(dst + q * sl) = p;
+  }
+}
+
+// the trailing amax word of a two-slice image and its scale (write_weight_image)
+template <int NS>
+__device__ __forceinline__ float weight_image_scale(unsigned short* Bx, int K, int Npad, unsigned word, int bits) {
+  if constexpr (NS == 2) {
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+      *reinterpret_cast<unsigned*>(Bx + (long)NS * Npad * K) =
+          word == 0u ? 0u : __float_as_uint(__builtin_ldexpf(__uint_as_float(word), bits));
+    return exp2_int(slice_scale_exp(word, bits));
+  }
+  return 1.f;
+}
+
+template <int NS>
+__global__ __launch_bounds__(256) void k_conv_weights_images_tiled(const ConvWeights* __restrict__ d) {
+  __shared__ float tile[WI_T][WI_LD];
+  const ConvWeights c = d[blockIdx.y];
+  const float* __restrict__ W = c.W;
+  const int Fout = c.Fout, Fin = c.Fin, ld = 3 * c.Fin;
+  const float a = c.fake_a, b = c.fake_b;
+  const unsigned word = NS == 2 ? *c.amax : 0u;
+  const int t = threadIdx.x;
+  const auto tiled = [](const unsigned short* Bx, int kdim) {
+    return Bx != nullptr && kdim % 16 == 0 && (reinterpret_cast<uintptr_t>(Bx) & 15) == 0;
+  };
+  const bool tf = tiled(c.Bx_f, Fin), tef = tiled(c.Bx_ef, Fin), tb = tiled(c.Bx_b, Fout), teb = tiled(c.Bx_eb, Fout);
+  // images that cannot take the tiled form: the element walk, all blocks of the layer
+  if (!tf)
+    write_weight_image<NS>(c.Bx_f, 3 * Fin, Fout, word, 0, [&](int k, int n) {
+      const int kk = k / Fin, fin = k - kk * Fin;
+      return W[(long)n * ld + fin * 3 + kk];
+    });
+  if (!tef)
+    write_weight_image<NS>(c.Bx_ef, Fin, Fout, word, c.eff_bits, [&](int k, int n) {
+      return weight_eff_value(W + (long)n * ld + k * 3, a, b);
+    });
+  if (!tb)
+    write_weight_image<NS>(c.Bx_b, 3 * Fout, Fin, word, 0, [&](int k, int n) {
+      const int kk = k / Fout, fo = k - kk * Fout;
+      return W[(long)fo * ld + n * 3 + kk];
+    });
+  if (!teb)
+    write_weight_image<NS>(c.Bx_eb, Fout, Fin, word, c.eff_bits, [&](int k, int n) {
+      return weight_eff_value(W + (long)k * ld + n * 3, a, b);
+    });
+  if (!(tf || tef || tb || teb)) return;
+  const int FoP = cdiv_dev(Fout, 128) * 128, FiP = cdiv_dev(Fin, 128) * 128;     // Npad of f / ef and of b / eb
+  const long sl_o = (long)FoP * 16, sl_i = (long)FiP * 16;                        // slice strides
+  float sc_f = 1.f, sc_ef = 1.f, sc_b = 1.f, sc_eb = 1.f;
+  if (tf) sc_f = weight_image_scale<NS>(c.Bx_f, 3 * Fin, FoP, word, 0);
+  if (tef) sc_ef = weight_image_scale<NS>(c.Bx_ef, Fin, FoP, word, c.eff_bits);
+  if (tb) sc_b = weight_image_scale<NS>(c.Bx_b, 3 * Fout, FiP, word, 0);
+  if (teb) sc_eb = weight_image_scale<NS>(c.Bx_eb, Fout, FiP, word, c.eff_bits);
+  const int nti = FiP / WI_T, nt = (FoP / WI_T) * nti;
+  for (int tl = blockIdx.x; tl < nt; tl += gridDim.x) {
+    const int fo0 = (tl / nti) * WI_T, fin0 = (tl - (tl / nti) * nti) * WI_T;
+    const bool has_o = fo0 < Fout, has_i = fin0 < Fin;       // the tile holds rows / columns of W
+    if (!has_o && !has_i) continue;                          // (block-uniform)
+    __syncthreads();                                         // the previous tile's readers are done
+    for (int e = t; e < WI_T * 3 * WI_T; e += 256) {
+      const int r = e / (3 * WI_T), cc = e - r * (3 * WI_T);
+      const int fo = fo0 + r, col = 3 * fin0 + cc;
+      tile[r][cc] = (fo < Fout && col < ld) ? W[(long)fo * ld + col] : 0.f;
+    }
+    __syncthreads();
+    // item j = half + 2 * nl + 64 * (g + 2 * kk): 8 values k = kbase + 16 g + 8 half + 0 .. 7 of column n = n0 + nl
+    if (has_i && (tf || tef)) {          // f, ef: k runs along fin, n = fo
+      for (int j = t; j < 64 * 2 * 4; j += 256) {
+        const int half = j & 1, nl = (j >> 1) & 31, g = (j >> 6) & 1, kk = j >> 7;      // kk == 3: the effective image
+        const int fl = 16 * g + 8 * half, fin = fin0 + fl, n = fo0 + nl;
+        if (fin >= Fin) continue;
+        float v[8];
+        if (kk < 3) {
+          if (!tf) continue;
+#pragma unroll
+          for (int e = 0; e < 8; e++) v[e] = n < Fout ? tile[nl][(fl + e) * 3 + kk] : 0.f;
+          const int k = kk * Fin + fin;
+          store_k8<NS>(c.Bx_f + (long)(k >> 4) * NS * sl_o + (long)n * 16 + (k & 15), sl_o, v, sc_f);
+        } else {
+          if (!tef) continue;
+#pragma unroll
+          for (int e = 0; e < 8; e++) v[e] = n < Fout ? weight_eff_value(&tile[nl][(fl + e) * 3], a, b) : 0.f;
+          store_k8<NS>(c.Bx_ef + (long)(fin >> 4) * NS * sl_o + (long)n * 16 + (fin & 15), sl_o, v, sc_ef);
+        }
+      }
+    }
+    if (has_o && (tb || teb)) {          // b, eb: k runs along fo, n = fin
+      for (int j = t; j < 64 * 2 * 4; j += 256) {
+        const int half = j & 1, nl = (j >> 1) & 31, g = (j >> 6) & 1, kk = j >> 7;
+        const int rl = 16 * g + 8 * half, fo = fo0 + rl, n = fin0 + nl;
+        if (fo >= Fout) continue;
+        float v[8];
+        if (kk < 3) {
+          if (!tb) continue;
+#pragma unroll
+          for (int e = 0; e < 8; e++) v[e] = n < Fin ? tile[rl + e][nl * 3 + kk] : 0.f;
+          const int k = kk * Fout + fo;
+          store_k8<NS>(c.Bx_b + (long)(k >> 4) * NS * sl_i + (long)n * 16 + (k & 15), sl_i, v, sc_b);
+        } else {
+          if (!teb) continue;
+#pragma unroll
+          for (int e = 0; e < 8; e++) v[e] = n < Fin ? weight_eff_value(&tile[rl + e][nl * 3], a, b) : 0.f;
+          store_k8<NS>(c.Bx_eb + (long)(fo >> 4) * NS * sl_i + (long)n * 16 + (fo & 15), sl_i, v, sc_eb);
+        }
+      }
+    }
+  }
+}
+
 // Block = 32 consecutive output elements x UNP_CG chunk groups: the partial buffers hold hundreds of chunks (one per
 // sample in row-set mode), so the chunk loop is split UNP_CG ways (4 loads in flight each) and reduced through LDS.
 // 8 groups (256 threads): alone on the GPU 32 groups are faster, but this kernel runs on the side stream next to the
@@ -2228,11 +2376,14 @@ extern "C" int p2m_conv_weights_prepare(const p2m_conv_weights* dev_desc, int32_
   const ConvWeights* d = reinterpret_cast<const ConvWeights*>(dev_desc);
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(96, n);                    // grid-stride over each image: the largest (768 x 256) is 768 elements per thread
+  const bool tiled = narrow_rows();          // the LDS-tiled form: the largest layer (256 x 256) is 64 tiles
   if (arith == P2M_ARITH_F16X2) {
     hipLaunchKernelGGL(k_conv_weights_amax, dim3(n), dim3(1024), 0, s, d);
-    hipLaunchKernelGGL(k_conv_weights_images<2>, grid, dim3(256), 0, s, d);
+    if (tiled) hipLaunchKernelGGL(k_conv_weights_images_tiled<2>, grid, dim3(256), 0, s, d);
+    else hipLaunchKernelGGL(k_conv_weights_images<2>, grid, dim3(256), 0, s, d);
   } else {
-    hipLaunchKernelGGL(k_conv_weights_images<3>, grid, dim3(256), 0, s, d);
+    if (tiled) hipLaunchKernelGGL(k_conv_weights_images_tiled<3>, grid, dim3(256), 0, s, d);
+    else hipLaunchKernelGGL(k_conv_weights_images<3>, grid, dim3(256), 0, s, d);
   }
   return check_launch("conv_weights_prepare");
 }

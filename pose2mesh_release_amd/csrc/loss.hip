@@ -94,10 +94,23 @@ __global__ __launch_bounds__(256) void k_pose_regress(LossArgs a) {
   if (threadIdx.x == 0) a.partial[3 * a.npart + blockIdx.x] = sl * a.s_joint;
 }
 
+// Logical block id of the two big kernels below (P2M_NARROW_ROWS = 1).  Block b runs on XCD b % 8, so in the plain order the ~54 /
+// ~27 blocks of one sample are spread over all eight L2s, and each of them fetches the sample's cam, gt and face_grad rows
+// through its own 12-byte gathers: the kernels moved 8 x their data.  With xcd_block_id a
+// sample's rows are fetched by one L2.  The thread <-> (b, face / vertex) mapping, the 256-index groups of the loss partials
+// and all arithmetic are those of the plain order.
+template <bool XCD>
+__device__ __forceinline__ int loss_block_id() {
+  if constexpr (XCD) return xcd_block_id(blockIdx.x, gridDim.x);
+  else return blockIdx.x;
+}
+
 // one thread per (b, face): normal + edge terms and their gradients w.r.t. the three corners
+template <bool XCD>
 __global__ __launch_bounds__(256) void k_face_terms(LossArgs a) {
   __shared__ float sh[4];
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  const int bid = loss_block_id<XCD>();
+  const long idx = (long)bid * 256 + threadIdx.x;
   float l_normal = 0.f, l_edge = 0.f;
   if (idx < (long)a.B * a.F) {
     const int b = (int)(idx / a.F), f = (int)(idx % a.F);
@@ -144,15 +157,17 @@ __global__ __launch_bounds__(256) void k_face_terms(LossArgs a) {
   const float sn = block_sum(l_normal, sh);
   const float se = block_sum(l_edge, sh);
   if (threadIdx.x == 0) {
-    a.partial[1 * a.npart + blockIdx.x] = sn * a.s_normal;
-    a.partial[2 * a.npart + blockIdx.x] = se * a.s_edge;
+    a.partial[1 * a.npart + bid] = sn * a.s_normal;
+    a.partial[2 * a.npart + bid] = se * a.s_edge;
   }
 }
 
 // one thread per (b, real vertex): vertex L1 + incident face gradients + joint-regressor term -> grad_cam
+template <bool XCD>
 __global__ __launch_bounds__(256) void k_vertex_grad(LossArgs a) {
   __shared__ float sh[4];
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  const int bid = loss_block_id<XCD>();
+  const long idx = (long)bid * 256 + threadIdx.x;
   float l_v = 0.f;
   if (idx < (long)a.B * a.nv) {
     const int b = (int)(idx / a.nv), v = (int)(idx % a.nv);
@@ -184,7 +199,7 @@ __global__ __launch_bounds__(256) void k_vertex_grad(LossArgs a) {
     }
   }
   const float sv = block_sum(l_v, sh);
-  if (threadIdx.x == 0) a.partial[0 * a.npart + blockIdx.x] = sv * a.s_vertex;
+  if (threadIdx.x == 0) a.partial[0 * a.npart + bid] = sv * a.s_vertex;
 }
 
 __global__ __launch_bounds__(256) void k_loss_finalize(const float* __restrict__ partial, int npart, int n0, int n1, int n2, int n3,
@@ -331,8 +346,13 @@ extern "C" int p2m_mesh_loss(const float* cam_mesh, int32_t V0, const int32_t* p
     }
   }
   hipLaunchKernelGGL(k_pose_regress, dim3(nb_pose), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(k_face_terms, dim3(nb_face), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(k_vertex_grad, dim3(nb_vert), dim3(256), 0, s, a);
+  if (narrow_rows()) {
+    hipLaunchKernelGGL(k_face_terms<true>, dim3(nb_face), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_vertex_grad<true>, dim3(nb_vert), dim3(256), 0, s, a);
+  } else {
+    hipLaunchKernelGGL(k_face_terms<false>, dim3(nb_face), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_vertex_grad<false>, dim3(nb_vert), dim3(256), 0, s, a);
+  }
   hipLaunchKernelGGL(k_loss_finalize, dim3(4), dim3(256), 0, s, a.partial, a.npart, nb_vert, nb_face, nb_face, nb_pose, losses);
   return check_launch("mesh_loss");
 }

@@ -11,6 +11,7 @@ namespace p2m {
 
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
+bool narrow_rows();     // P2M_NARROW_ROWS, capi.hip
 
 // Tile plan of the LDS-staged basis kernel (k_basis_tile): the real rows, in compact order, are cut into tiles of
 // consecutive rows whose merged-CSR neighbourhoods have a small UNION (the coarsening-tree order keeps neighbours
@@ -121,6 +122,12 @@ static inline RowSet row_set_of(const Graph& g, int which) {
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 #ifdef __HIPCC__
 __device__ __forceinline__ int cdiv_dev(int a, int b) { return (a + b - 1) / b; }
+// Observed dispatch: block b runs on XCD b % 8.  Logical id that gives every XCD a contiguous range of [0, nb), for any nb (the
+// first nb % 8 XCDs take one block more): neighbouring logical blocks then share one L2.  A bijection of [0, nb).
+__device__ __forceinline__ int xcd_block_id(int bid, int nb) {
+  const int x = bid & 7, q = nb >> 3, r = nb & 7;
+  return x * q + (x < r ? x : r) + (bid >> 3);
+}
 #endif
 
 #ifdef __HIPCC__
