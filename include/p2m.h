@@ -902,6 +902,81 @@ int p2m_mesh_render(const float* verts, const int32_t* faces, int32_t nf, const 
                     uint8_t* image, int32_t* face_id, int32_t* mesh_id, float* depth, int32_t* status, void* workspace,
                     void* stream);
 
+/* ---- Shading a visibility buffer: vertex normals, smooth shading, vertex colours, attributes, wireframe (csrc/shade.hip) ---
+ * A second, deferred pass over what p2m_mesh_render wrote (face_id, mesh_id): the reference's smooth-shaded result figures
+ * (asset/quality_result.png), the `wireframe` switch of demo/renderer.py (RenderFlags.ALL_WIREFRAME) and any per-vertex
+ * quantity carried to the pixels (an error as colour, part labels, skinning weights, normal maps, correspondences).  As above,
+ * the reference's own renderer cannot run here: this comment is the contract and tests/shade_ref.py its numpy restatement.
+ * Both calls: one memset node and one kernel on `stream`, no allocation, no synchronisation, grids from shapes only (capturable);
+ * no float atomics and no LDS atomics, so a result is reproducible bit for bit and a mesh's values do not depend on the batch
+ * around it.
+ *
+ * p2m_vertex_normals: area-weighted unit vertex normals of B meshes that share one face list.
+ *   verts [B, nv, 3] fp32, faces [nf, 3] int32; vf_ptr int32 [nv + 1], vf_idx int32 [n_idx]: the vertex-to-face table - vertex v
+ *   lists the ids of its incident faces, ascending, in vf_idx[vf_ptr[v] .. vf_ptr[v + 1]) (a CSR; render.vertex_face_table builds
+ *   it); normals [B, nv, 3] fp32; status int32 [B] or NULL.  All device memory.  In fp64, every operation rounded once (nothing
+ *   fused), for vertex v of mesh b: for each listed face f = (i0, i1, i2) in table order, with p_k the fp32 vertices widened,
+ *     a = p1 - p0,  b = p2 - p0,  c = (ay bz - az by,  az bx - ax bz,  ax by - ay bx)    (two products and one difference each)
+ *     n += c                                                                           (component-wise, from n = 0)
+ *   then q = (nx nx + ny ny) + nz nz and normal = (float)(n / sqrt(q)), the division and the square root correctly rounded.
+ *   If q is 0 or not finite (an isolated vertex, cancelling faces, a NaN or overflowing input) the normal is (0, 0, 0) and status
+ *   bit 0 of the mesh is set.  A table entry outside [0, nf), a face with an index outside [0, nv), or a vertex whose table range
+ *   is not inside [0, n_idx] contributes nothing, is never used as an index, and sets status bit 1 of the mesh.  The normals are
+ *   the mesh's own: they are not turned towards a viewer.  A gather (one thread per vertex): no float atomics.
+ *   Errors (P2M_ERR_INVALID, nothing launched): NULL pointers (status may be NULL; vf_idx when n_idx = 0), B < 0, more than 65535
+ *   meshes, nv < 1, nf < 1, n_idx < 0, B nv 3 >= 2^31, a buffer not 4-byte aligned, an output that overlaps an input or the other
+ *   output.
+ *
+ * p2m_mesh_shade: one pass over the pixels of a visibility buffer.
+ *   face_id, mesh_id int32 [n, H, W] as p2m_mesh_render writes them (n = B, or 1 in scene mode); verts, faces, nf, cam, B, nv, H,
+ *   W, mode, lights (HOST array), nl, ambient, background, bg_per_mesh exactly as that call took them.  Each of the following may
+ *   be NULL / 0 when unused:
+ *     colours [B, 3] fp32 or vertex_colours fp32 [B, nv, 3] (vertex_colours_shared = 0) / [nv, 3] for all meshes (= 1): an image
+ *                     takes exactly one of the two
+ *     normals [B, nv, 3] fp32 (p2m_vertex_normals' output, or any other): NULL means flat shading
+ *     attrs   [B, nv, C] fp32, 1 <= C <= 16
+ *     wire_T  int32 in [0, 2^16]: the line's half width in 1/256 pixel, 0: no wire;  wire_rgb: HOST uint8[3];  wire_only: a flag
+ *     attr_fill: what attr_out shows off the mesh
+ *   Outputs, each may be NULL: image uint8 [n, H, W, 3], bary fp32 [n, H, W, 3], attr_out fp32 [n, H, W, C], status int32 [B].
+ *   OFF THE MESH.  A pixel with face_id < 0 shows the background (NULL: zeros), bary = 0 and attr_out = attr_fill.  A pixel with
+ *   face_id >= nf, with mesh_id outside [0, B), whose face has an index outside [0, nv) or area2 = 0 (none of which the rasteriser
+ *   writes) is treated the same way and sets status bit 1 of mesh 0; such a value is never used as an index.  The mesh of a
+ *   covered pixel is mesh_id's value in both modes (in batch mode p2m_mesh_render wrote the image's own index there).
+ *   BARYCENTRICS.  For a covered pixel of mesh b and face f: X, Y of the three vertices by the projection and snap above (the same
+ *   code), area2, s and E_0, E_1, E_2 at the pixel centre exactly as defined above (integers), then in fp32, conversions and
+ *   divisions correctly rounded,
+ *     l0 = (float)E_1 / (float)|area2|,  l1 = (float)E_2 / (float)|area2|,  l2 = (float)E_0 / (float)|area2|     bary = (l0, l1, l2)
+ *   the weights of v0, v1, v2; l1 and l2 are the ones of the depth formula.
+ *   ATTRIBUTES.  attr_out[c] = fmaf(l2, a2[c], fmaf(l1, a1[c], l0 * a0[c])) in fp32, a_k the attribute rows of the face's vertices.
+ *   WIRE (wire_T = T > 0).  The pixel is on the wire iff E_k^2 <= T^2 (A_k^2 + B_k^2) for some edge k of its own visible face,
+ *   decided exactly in 128-bit integers (equality is on the wire): the centre lies within T / 256 pixel of the edge's line.  Only
+ *   the visible face's edges are tested: hidden lines are removed, an interior edge is 2 T wide (T from each neighbour), a
+ *   silhouette edge T.  A wire pixel shows wire_rgb, unshaded; with wire_only a covered pixel off the wire shows the background.
+ *   SHADING of the other covered pixels, in fp64, each operation rounded once, with dk = (double)lk:
+ *     colour  c = colours[b], or per channel c = (d0 c0 + d1 c1) + d2 c2 of the vertices' colours
+ *     normal  without normals: the unit face normal turned towards the viewer, and I, exactly as p2m_mesh_render computes them;
+ *             with normals:  m = (d0 n0 + d1 n1) + d2 n2 per component,  q = (mx mx + my my) + mz mz;  q zero or not finite: the
+ *             face normal as above;  otherwise u = m / sqrt(q), negated when the face is back-facing (area2 sgn(ax ay) > 0:
+ *             visible only where the rasteriser did not cull), and
+ *             I = ambient + sum_l k_l max(0, (ux lx + uy ly) + uz lz)   accumulated in the lights' order
+ *     rgb_c = floor(255 min(1, c_c I) + 0.5)                             (the rasteriser's rounding: negative and NaN give 0)
+ *   With no normals, no vertex_colours and no wire, image is bit for bit the image p2m_mesh_render wrote.
+ *   ALIASING.  image may be the very buffer the rasteriser wrote (the pass never reads it).  No output may overlap an input or
+ *   another output.
+ *   Errors (P2M_ERR_INVALID, nothing launched): as for p2m_mesh_render (NULL face_id, mesh_id, verts, faces or cam, the shape
+ *   limits, nl, a zero or non-finite light direction, a per-mesh background in scene mode), and: C outside [1, 16] with attrs,
+ *   attr_out without attrs, wire_T outside [0, 2^16] or wire_T > 0 without wire_rgb, both or neither of colours / vertex_colours
+ *   with an image, a buffer not 4-byte aligned (image and background: 1 byte), an output that overlaps an input or an output.  */
+enum { P2M_SHADE_DEGENERATE = 1, P2M_SHADE_BAD_INDEX = 2 };
+int p2m_vertex_normals(const float* verts, const int32_t* faces, const int32_t* vf_ptr, const int32_t* vf_idx, int32_t n_idx,
+                       int32_t B, int32_t nv, int32_t nf, float* normals, int32_t* status, void* stream);
+int p2m_mesh_shade(const int32_t* face_id, const int32_t* mesh_id, const float* verts, const int32_t* faces, int32_t nf,
+                   const float* cam, const float* colours, const float* vertex_colours, int32_t vertex_colours_shared,
+                   const float* normals, const float* lights, int32_t nl, float ambient, const float* attrs, int32_t C,
+                   int32_t wire_T, const uint8_t* wire_rgb, int32_t wire_only, const uint8_t* background, int32_t bg_per_mesh,
+                   float attr_fill, int32_t B, int32_t nv, int32_t H, int32_t W, int32_t mode, uint8_t* image, float* bary,
+                   float* attr_out, int32_t* status, void* stream);
+
 /* ---- The demo's camera: batched 2D-pose preparation and the L1 Adam fit (csrc/camfit.hip) ---------------------------------
  * The piece of demo/run.py between its two device halves (optimize_cam_param, :149-197): pixels of 2D joints -> the network's
  * input and the fit's target (p2m_pose_prepare); 3D joints + target -> the weak-perspective camera of the crop

@@ -141,6 +141,9 @@ HIP_SYMBOLS = {
     "p2m_mesh_render_workspace": (_c.c_int, [_i32, _i32, _i32, _i32, _i32, _c.POINTER(_i64)]),
     "p2m_mesh_render": (_c.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _i32, _vp, _i32, _i32, _i32, _i32,
                                    _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "p2m_vertex_normals": (_c.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "p2m_mesh_shade": (_c.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _f32, _vp, _i32, _i32, _vp, _i32,
+                                  _vp, _i32, _f32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "p2m_pose_prepare": (_c.c_int, [_vp, _i32, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "p2m_camera_fit": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, FitSchedule, _i32, _f32, _f64, _f64, _f64, _vp, _vp, _vp,
                                   _vp]),

@@ -17,7 +17,7 @@
 //                   the order of arrival, so the result is reproducible bit for bit.  The tile is then resolved to the
 //                   outputs row by row.
 //   k_render_project  (p2m_mesh_project) one thread per (mesh, vertex): the same projection and snap, for callers and tests.
-#include "p2m_common.h"
+#include "p2m_render.h"
 
 namespace p2m {
 
@@ -25,11 +25,6 @@ constexpr int R_NT = 256;             // threads per block
 constexpr int R_TILE = 64;            // tile edge in pixels: 4096 keys x 8 B = 32 KB of LDS
 constexpr int R_QCAP = 2 * R_NT;      // queue of hit faces: flushed as soon as a scan step could overflow it
 constexpr int R_BIG = 256;            // clipped bbox pixels above which a face is rasterised by the whole block
-constexpr int R_FIX = 256;            // sub-pixel units per pixel
-constexpr int R_CLAMP = 1 << 23;      // snapped coordinates are clamped to +-2^23
-constexpr int R_MAX_LIGHTS = 4;
-constexpr int R_MAX_DIM = 8192;
-constexpr int R_STATUS_CLAMPED = 1, R_STATUS_BAD_INDEX = 2;
 
 struct FaceRec {                      // 48 bytes: three 16-byte loads
   int x0, y0, x1, y1;
@@ -37,27 +32,7 @@ struct FaceRec {                      // 48 bytes: three 16-byte loads
   float z2; unsigned rgb; int pad0, pad1;
 };
 
-// ---- projection and snap (shared by setup and project: bitwise the same) ------------------------------------------------
-struct CamCoef { double ax, bx, ay, by; };
-
-__device__ __forceinline__ CamCoef cam_coef(const float* cam, int H, int W) {
-  const double sx = (double)cam[0], sy = (double)cam[1], tx = (double)cam[2], ty = (double)cam[3];
-  const double hw = 0.5 * (double)W, hh = 0.5 * (double)H;
-  CamCoef c;                          // (each operation rounded once: no contraction)
-  c.ax = __dmul_rn(hw, sx);
-  c.bx = __dmul_rn(hw, __dadd_rn(1.0, __dmul_rn(sx, tx)));
-  c.ay = __dmul_rn(hh, sy);
-  c.by = __dmul_rn(hh, __dadd_rn(1.0, __dmul_rn(sy, ty)));
-  return c;
-}
-
-__device__ __forceinline__ int snap(double a, double v, double b, bool& clamped) {
-  const double t = rint(__dmul_rn((double)R_FIX, __fma_rn(a, v, b)));    // ties to even
-  if (!(t <= (double)R_CLAMP)) { clamped = true; return R_CLAMP; }      // (NaN lands here)
-  if (t < -(double)R_CLAMP) { clamped = true; return -R_CLAMP; }
-  return (int)t;
-}
-
+// ---- projection and snap: cam_coef / snap of p2m_render.h (shared with shade.hip: bitwise the same) -----------------------
 __global__ __launch_bounds__(R_NT) void k_render_project(const float* __restrict__ verts, const float* __restrict__ cam, int B,
                                                          int nv, int H, int W, int* __restrict__ xy_fix,
                                                          int* __restrict__ status) {
@@ -74,13 +49,6 @@ __global__ __launch_bounds__(R_NT) void k_render_project(const float* __restrict
 }
 
 // ---- per-face setup --------------------------------------------------------------------------------------------------
-struct Lights {
-  int nl;
-  double ambient;
-  double dir[R_MAX_LIGHTS][3];        // unit vectors towards the lights
-  double k[R_MAX_LIGHTS];
-};
-
 struct SetupArgs {
   const float* verts; const int* faces; const float* cam; const float* colours;
   int B, nv, nf, H, W, cull;
@@ -90,12 +58,6 @@ struct SetupArgs {
   int* mbox;                          // [B][4]   min x0, min y0, min -x1, min -y1 over the kept faces (memset to 0x7f bytes)
   int* status;                        // [B] or NULL
 };
-
-__device__ __forceinline__ unsigned to_u8(double v) {                    // floor(255 min(1, v) + 0.5), negative and NaN -> 0
-  const double c = v < 1.0 ? v : 1.0;
-  const double r = floor(255.0 * c + 0.5);
-  return r > 0.0 ? (unsigned)r : 0u;
-}
 
 __global__ __launch_bounds__(R_NT) void k_render_setup(SetupArgs a) {
   const int m = blockIdx.y;
@@ -131,22 +93,7 @@ __global__ __launch_bounds__(R_NT) void k_render_setup(SetupArgs a) {
         const int jy0 = max((ymin - R_FIX / 2 + R_FIX - 1) >> 8, 0), jy1 = min((ymax - R_FIX / 2) >> 8, a.H - 1);
         if (jx0 <= jx1 && jy0 <= jy1) {
           bx0 = jx0; by0 = jy0; bx1 = jx1; by1 = jy1;
-          // flat shading: the fp64 unit normal turned towards the viewer (n_z <= 0), I = ambient + sum k max(0, n.l)
-          const double e1[3] = {(double)p[1][0] - (double)p[0][0], (double)p[1][1] - (double)p[0][1], (double)p[1][2] - (double)p[0][2]};
-          const double e2[3] = {(double)p[2][0] - (double)p[0][0], (double)p[2][1] - (double)p[0][1], (double)p[2][2] - (double)p[0][2]};
-          double n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-          const double len = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
-          double I = a.L.ambient;
-          if (len > 0.0) {
-            const double s = (n[2] > 0.0 ? -1.0 : 1.0) / len;
-#pragma unroll
-            for (int l = 0; l < R_MAX_LIGHTS; l++) {
-              if (l < a.L.nl) {
-                const double d = s * (n[0] * a.L.dir[l][0] + n[1] * a.L.dir[l][1] + n[2] * a.L.dir[l][2]);
-                I += a.L.k[l] * (d > 0.0 ? d : 0.0);
-              }
-            }
-          }
+          const double I = face_intensity(p, a.L);                      // flat shading (p2m_render.h)
           const float* col = a.colours + 3 * m;
           FaceRec r;
           r.x0 = x[0]; r.y0 = y[0]; r.x1 = x[1]; r.y1 = y[1]; r.x2 = x[2]; r.y2 = y[2];
@@ -470,19 +417,7 @@ extern "C" int p2m_mesh_render(const float* verts, const int32_t* faces, int32_t
   SetupArgs sa;
   sa.verts = verts; sa.faces = faces; sa.cam = cam; sa.colours = colours;
   sa.B = B; sa.nv = nv; sa.nf = nf; sa.H = H; sa.W = W; sa.cull = flags & 1;
-  sa.L.nl = nl; sa.L.ambient = (double)ambient;
-  for (int l = 0; l < R_MAX_LIGHTS; l++) {
-    double d[3] = {0.0, 0.0, 0.0}, k = 0.0;
-    if (l < nl) {
-      for (int c = 0; c < 3; c++) d[c] = (double)lights[4 * l + c];
-      k = (double)lights[4 * l + 3];
-      const double len = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-      P2M_CHECK_ARG(len > 0.0 && len < __builtin_inf(), "a light direction must be non-zero and finite");
-      for (int c = 0; c < 3; c++) d[c] /= len;
-    }
-    for (int c = 0; c < 3; c++) sa.L.dir[l][c] = d[c];
-    sa.L.k[l] = k;
-  }
+  P2M_CHECK_ARG(lights_from_host(lights, nl, ambient, sa.L), "a light direction must be non-zero and finite");
   char* w = (char*)workspace;
   sa.fbox = (short4*)w;
   sa.frec = (FaceRec*)(w + render_rec_bytes(B, nf));
