@@ -1221,6 +1221,58 @@ int p2m_crowd_select(const float* dets, const int32_t* num, int32_t B, int32_t P
                      int32_t* index, int8_t* reason, int32_t* dup_of, double* score, uint8_t* keep, void* stream);
 int p2m_person_colours(const uint64_t* state, int32_t n, double s, double v, float* rgb, uint8_t* u8, void* stream);
 
+/* ---- Tracking people across frames: stable slots and ids (csrc/track.hip) ------------------------------------------------------
+ * p2m_crowd_select hands out the people of a frame in the detector's list order, which changes from frame to frame; the
+ * streaming filter p2m_one_euro needs row b to be the same person in every call.  p2m_pose_track joins them: a state machine
+ * per video stream that gives every person a track SLOT that stays theirs and a unique id.  The reference has no tracker (its
+ * 3DPW data carries person ids): the contract below is this project's, tests/track_ref.py restates it in numpy, float64.  One
+ * block per stream, one launch per call on `stream`, no allocation, no synchronisation, the grid from the shapes alone
+ * (capturable).  The first call on a device opts the kernel in to its largest LDS size (no stream operation).
+ *
+ *   people fp32 [F, S, P, Jo, 3] = (x, y, confidence): F >= 1 frames of each of S streams, up to P <= 64 people per frame,
+ *   Jo <= 64 joints - p2m_crowd_select's joints: [1, B, ..] for one frame of B streams, [B, 1, ..] for B frames of one video.
+ *   A person slot is PRESENT iff all its 3 Jo values are finite; absent slots may sit anywhere in the list.
+ *   State, device memory of the caller's, persistent across calls, updated in place:  pose fp32 [S, T, Jo, 3];  uid int32
+ *   [S, T], -1 = a free slot;  missed int32 [S, T];  next_uid int32 [S];  T <= 64 track slots per stream.  A fresh state is
+ *   uid = -1, missed = 0, next_uid = 0 (pose is never read of a free slot).
+ *   pose_thr, gate, min_common, max_missed: 0.1, 0.3, 3, 10 are this project's defaults - a choice, not measured optima.
+ *
+ *   Per stream, the frames of a call in order.  ALL DECISION ARITHMETIC IS FLOAT64 on the fp32 values widened exactly, every
+ *   operation rounded once and none fused (this unit is built with -ffp-contract=off):
+ *     valid      a joint of a person, or of a stored track pose, is valid iff conf > pose_thr (strict)
+ *     cost(p, t) of a present person p and an alive track t (uid >= 0 AT THE START of the frame): the terms |v_p - v_t| for
+ *                v = x_j, y_j of every joint j valid in both, walked JOINT-MAJOR, x BEFORE y.  Every term counts, a zero too
+ *                (unlike p2m_crowd_select's duplicate test).  S = the terms added sequentially in that order, n = their number
+ *                (twice the common joints).  n < 2 min_common: no candidate.  size_t = max(max x - min x, max y - min y) over
+ *                the track's valid joints; if size_t >= 1 is false, size_t = 1.  cost = (S / n) / size_t, two correctly rounded
+ *                divisions.  The pair is a candidate iff cost < gate (strict).
+ *     greedy     globally ascending: repeatedly the candidate pair of least cost among the persons and tracks not yet taken;
+ *                ties go to the lower track slot, then to the lower person index; until no candidate is left.
+ *     births     the present persons left unmatched, in person order, each take the lowest slot that was free AT THE START of
+ *                the frame; a born slot gets uid = next_uid[s]++.  With no such slot left the person is dropped (slot_of = -2,
+ *                counted in dropped).
+ *     update     a slot with a person takes that person's Jo x 3 values bit for bit (low-confidence joints too), missed = 0.
+ *                An alive slot without one: missed += 1, and it is retired (uid = -1; missed keeps its value) when
+ *                missed > max_missed.  A slot retired in a frame is free from the NEXT frame on, never within it.
+ *   Outputs per frame, each may be NULL:
+ *     joints fp32 [F, S, T, Jo, 3]  the slot's person this frame; quiet NaNs (7FC00000) otherwise, which the modules behind
+ *                                   read as "nobody" (see p2m_crowd_select)
+ *     slot_of int32 [F, S, P]       the person's slot; -1 absent, -2 dropped
+ *     person_of int32 [F, S, T]     the slot's person, -1 none
+ *     uid int32 [F, S, T]           after the frame
+ *     flags uint8 [F, S, T]         bit 0 alive after the frame, bit 1 has a person this frame, bit 2 born, bit 3 FRESH = has a
+ *                                   person and (born or missed > 0 before the frame), bit 4 retired this frame
+ *     cost fp64 [F, S, T]           the matched pair's cost; the quiet NaN 7FF8000000000000 for a born or empty slot
+ *     dropped int32 [F, S]
+ *   A stream's results depend on that stream alone; F frames in one call equal F calls of one frame bit for bit, state
+ *   included; everything is reproducible bit for bit (no atomics; the greedy arg-min is an exact comparison of (cost, t, p)).
+ *   Errors (P2M_ERR_INVALID, nothing launched): NULL people or a NULL state pointer, F or S outside [1, 2^24], P, T or Jo
+ *   outside [1, 64], min_common outside [1, Jo], max_missed < 0, pose_thr or gate not finite, cost not 8-byte aligned.       */
+int p2m_pose_track(const float* people, int32_t F, int32_t S, int32_t P, int32_t T, int32_t Jo, double pose_thr, double gate,
+                   int32_t min_common, int32_t max_missed, float* st_pose, int32_t* st_uid, int32_t* st_missed,
+                   int32_t* st_next_uid, float* joints, int32_t* slot_of, int32_t* person_of, int32_t* uid, uint8_t* flags,
+                   double* cost, int32_t* dropped, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -156,6 +156,8 @@ HIP_SYMBOLS = {
     "p2m_crowd_select": (_c.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _vp]),
     "p2m_person_colours": (_c.c_int, [_vp, _i32, _f64, _f64, _vp, _vp, _vp]),
+    "p2m_pose_track": (_c.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _f64, _f64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _vp, _vp, _vp, _vp, _vp]),
 }
 
 HOST_SYMBOLS = {

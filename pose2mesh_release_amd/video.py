@@ -121,7 +121,7 @@ class OneEuroFilter:
     """f = OneEuroFilter(min_cutoff=1.0, beta=0.0, d_cutoff=1.0, dt=1.0)
     y = f(x)                 x [B, ...]: one new frame for each of B tracks (e.g. [B, 6890, 3] from GraphedInference)
     y = f(x, chunk=True)     x [T, B, ...]: T frames per track; y has x's shape
-    f.reset();  f.reset(track_ids)
+    f.reset();  f.reset(track_ids);  f.reset(mask=m)
 
     The streaming form of the filter.  The first call fixes B and the per-track shape; the state (previous value and
     derivative per coordinate, a `started` flag per track) lives on the device, and a track's first frame after
@@ -130,7 +130,7 @@ class OneEuroFilter:
     y is a static buffer per input shape, overwritten by the next call of that shape (pass out= to keep a result).  After
     one call of a shape (which allocates), a call launches two kernels on the current stream and nothing else: it can be
     captured in torch.cuda.graph.  reset() is a device-side fill; reset(track_ids) takes a host sequence (one small copy)
-    or a CUDA index tensor (no copy)."""
+    or a CUDA index tensor (no copy); reset(mask=) a bool CUDA tensor [B] (a masked fill, capturable)."""
 
     def __init__(self, min_cutoff=1.0, beta=0.0, d_cutoff=1.0, dt=1.0):
         self.min_cutoff, self.beta, self.d_cutoff, self.dt = float(min_cutoff), float(beta), float(d_cutoff), float(dt)
@@ -190,8 +190,21 @@ class OneEuroFilter:
         return y
 
     @torch.no_grad()
-    def reset(self, track_ids=None):
-        """Restarts every track, or the given ones: their next frame passes through and initialises the filter."""
+    def reset(self, track_ids=None, mask=None):
+        """Restarts every track, or the given ones: their next frame passes through and initialises the filter.  mask: a bool
+        CUDA tensor [B] instead of track_ids - the tracks where it is set restart (a masked fill: data-independent, no copy,
+        capturable; track.PoseTracker's out.fresh.reshape(-1) is such a mask)."""
+        if mask is not None:
+            if track_ids is not None:
+                raise ValueError("give track_ids or mask, not both")
+            if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
+                raise _lib.P2MError("mask: the video kernels need a CUDA tensor (there is no CPU path)")
+            if self._state is None:
+                return
+            if mask.dtype != torch.bool or tuple(mask.shape) != (self.B,) or mask.device != self._dev:
+                raise ValueError(f"mask: expected a bool tensor [{self.B}] on {self._dev}")
+            self._state[2].masked_fill_(mask, 0)
+            return
         if self._state is None:
             return
         started = self._state[2]
