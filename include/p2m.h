@@ -552,6 +552,46 @@ int p2m_mesh_fscore(const float* pred_mesh, const float* gt_mesh, int32_t B, int
 int p2m_point_nn(const float* A, const float* B, int32_t nb, int32_t nA, int32_t nB, float* dAB, float* dBA, void* workspace,
                  int64_t workspace_bytes, void* stream);
 
+/* ---- error profiles: per-point errors, PCK histograms, running per-group and per-point totals (csrc/profile.hip) ---------
+ * What PCK curves, their AUC (FreiHAND's other two columns), PCK at a cut-off (MPI-INF-3DHP's PCK@150 mm), per-joint error
+ * tables and a dataset-mean per-vertex error map are derived from.  Neither the reference nor the FreiHAND server code is
+ * in this tree: this comment is the definition and tests/profile_ref.py its float64 restatement.
+ * pred, gt [B, N, 3] fp32, corresponding points; gt is read as gt * gt_scale (the product of two fp32 values, exact in
+ * fp64).  valid [B, N] uint8 or NULL: a point with valid == 0 is not counted (its error is written as 0, its coordinates
+ * are never read).  thresholds: DEVICE array t[0 .. K-1] of fp64, finite and ascending, 2 <= K <= 256; the caller uploads it
+ * from the host, so a table such as linspace(lo, hi, steps) arrives bit for bit (the order is the caller's contract: it is
+ * not checked on the device, and whatever the table holds every bin stays inside [0, K]).
+ * Per sample b < B_real, all in fp64:
+ *   1. root >= 0: both sets minus their own point `root` (root == -1: as they are)
+ *   2. align != 0: the prediction is similarity-aligned onto the ground truth over the counted points: centroids cP, cG,
+ *      H = sum (p - cP)(g - cG)^T / n, varP = sum |p - cP|^2 / n, the solve of p2m_rigid_align / p2m_mesh_eval's pa_mesh;
+ *      p <- c R p + t.  All counted points of the prediction coincide: c is non-finite and so is every error of the sample
+ *   3. e_i = sqrt(dx dx + dy dy + dz dz), d = p_i - g_i: three products and two sums, left to right, no fma contraction
+ *   4. bin_i = the number of thresholds < e_i, i.e. the first k with e_i <= t[k], and K if there is none (non-strict, unlike
+ *      the F-score's comparison).  A non-finite e_i goes to bin K
+ *   error [B, N] = e (0 where not counted), sample_pck [B, K + 1] int32 = the points of the sample per bin,
+ *   sample_mean [B] = the sum of e over the counted points / their number (NaN when there is none), the sum taken in a fixed
+ *   order: lane l of 256 adds its points l, l + 256, ... in ascending order (a point that is not counted adds 0), the 64 lanes
+ *   of a wave are added by the xor butterfly 32, 16, 8, 4, 2, 1, then the four wave totals in wave order.
+ * Running totals, ADDED to by launches behind the per-sample one, in sample order, starting from the value found there (so two
+ * calls over 4 and 5 samples leave bitwise the state of one call over the 9):
+ *   group_sum [n_groups + 1] fp64, group_count [n_groups + 1] int64, group_hist [n_groups + 1][K + 1] int64 (all three or
+ *     none): row 0 all samples, row 1 + g the samples with group[b] == g (group: [B] int32 or NULL; ids outside [0, n_groups)
+ *     count in row 0 only): the per-sample sums, the points counted, the bins
+ *   point_sum [N] fp64, point_count [N] int64, point_hist [N][K + 1] int64 (all three or none): over all samples, per point:
+ *     its errors, the samples that count it, its bins
+ * Integer sums only in the histograms (LDS integer atomics per sample); no float atomics, no allocation, no synchronisation
+ * (capturable); bitwise reproducible.  Rows b >= B_real are padding: never read, their outputs written as 0, not counted.
+ * workspace: p2m_error_profile_workspace(B, N) bytes of device memory, 16-byte aligned (-1 for B < 0 or N < 1).
+ * Errors (P2M_ERR_INVALID, nothing launched): NULL required pointers, N < 1, B_real outside [0, B], K outside 2..256, root
+ * outside [-1, N), B * N * 3 >= 2^31, incomplete totals, n_groups outside 0..65535, a workspace too small or misaligned.    */
+int64_t p2m_error_profile_workspace(int32_t B, int32_t N);
+int p2m_error_profile(const float* pred, const float* gt, const uint8_t* valid, int32_t B, int32_t B_real, int32_t N,
+                      float gt_scale, int32_t root, int32_t align, const double* thresholds, int32_t K, void* workspace,
+                      int64_t workspace_bytes, double* error, double* sample_mean, int32_t* sample_pck, const int32_t* group,
+                      int32_t n_groups, double* group_sum, int64_t* group_count, int64_t* group_hist, double* point_sum,
+                      int64_t* point_count, int64_t* point_hist, void* stream);
+
 /* ---- PoseNet, the 2D -> 3D lifter in front of MeshNet (lib/models/posenet.py:11-92) ---------------------------------
  * A 4096-wide residual MLP over B rows.  Every Linear (posenet.py:19,22,59,68: F.linear and its autograd) is a
  * weight-streaming contraction at these batch sizes and runs on p2m_gemm_tn, the reduction-split contraction with both

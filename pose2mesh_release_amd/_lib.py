@@ -119,6 +119,9 @@ HIP_SYMBOLS = {
     "p2m_mesh_fscore": (_c.c_int, [_vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32,
                                    _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "p2m_point_nn": (_c.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "p2m_error_profile_workspace": (_i64, [_i32, _i32]),
+    "p2m_error_profile": (_c.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _i32, _i32, _vp, _i32, _vp, _i64, _vp, _vp, _vp,
+                                     _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "p2m_body_sample_tile": (_i32, []),
     "p2m_body_vertex_tile": (_i32, []),
     "p2m_body_workspace": (_i64, [_i32, _i32, _i32]),

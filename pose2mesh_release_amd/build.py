@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 HIP_SOURCES = ["capi.hip", "basis.hip", "gemm.hip", "bn.hip", "optim.hip", "loss.hip", "chebtile.hip", "posenet.hip",
                "eval.hip", "body.hip", "body_bwd.hip", "fscore.hip", "sample.hip", "render.hip", "camfit.hip", "video.hip",
-               "overlay.hip", "annot.hip", "crowd.hip", "shade.hip", "track.hip"]
+               "overlay.hip", "annot.hip", "crowd.hip", "shade.hip", "track.hip", "profile.hip"]
 # per-source flags.  chebtile.hip: the gather's fmaf chains must stay scalar v_fma_f32 - SLP-packed v_pk_fma_f32 next to the
 # MFMA waves measured 9 % slower over the real-row shapes of a train step (17.2 vs 19.0 ms)
 # fscore.hip: the search loop is 6.5 plain f32 instructions per pair (3 v_sub, v_mul, 2 v_fmac, half a v_min3); SLP-packed it
@@ -31,10 +31,12 @@ HIP_SOURCES = ["capi.hip", "basis.hip", "gemm.hip", "bn.hip", "optim.hip", "loss
 # shade.hip: the same contract for the vertex normals, the barycentric attributes and the smooth shading, which are compared bit
 # for bit with tests/shade_ref.py (the flat intensity it shares with render.hip keeps that unit's contraction: p2m_render.h)
 # track.hip: the same contract for the tracker's float64 pair costs, which are compared exactly with tests/track_ref.py
+# profile.hip: the same contract for the error profile's float64 errors dx dx + dy dy + dz dz, whose bins and sums are compared
+# exactly with tests/profile_ref.py
 HIP_SOURCE_FLAGS = {"chebtile.hip": ["-fno-slp-vectorize"], "fscore.hip": ["-fno-slp-vectorize"],
                     "camfit.hip": ["-ffp-contract=off"], "video.hip": ["-ffp-contract=off"],
                     "crowd.hip": ["-ffp-contract=off"], "shade.hip": ["-ffp-contract=off"],
-                    "track.hip": ["-ffp-contract=off"]}
+                    "track.hip": ["-ffp-contract=off"], "profile.hip": ["-ffp-contract=off"]}
 HIP_HEADERS = ["p2m_common.h", "p2m_body.h", "p2m_split.h", "p2m_eval.h", "p2m_philox.h", "p2m_render.h", os.path.join("..", "..", "include", "p2m.h")]
 HIP_LIB = os.path.join(LIBDIR, "libp2m_hip.so")
 HOST_LIB = os.path.join(LIBDIR, "libp2m_host.so")

@@ -17,6 +17,13 @@ data/Human36M/dataset.py:514-572, lib/coord_utils.py:127-149).
   nearest_distances(A, B)                       the bare two-way nearest-point search between [N, 3] / [nb, N, 3] and
                                                 [M, 3] / [nb, M, 3] CUDA tensors (p2m_point_nn): chamfer distances,
                                                 per-vertex error heat maps.
+  ErrorProfile                                  where the error sits and how it is distributed (p2m_error_profile): per-point
+                                                errors between corresponding points, raw or similarity-aligned, binned against
+                                                an fp64 threshold table; running per-group and per-point sums, counts and
+                                                histograms; summary() syncs once and derives means, PCK curves and their AUC
+                                                (FreiHAND's AUC columns, PCK@150 mm, per-joint tables, the dataset-mean
+                                                per-vertex error map).  Defined in include/p2m.h, restated in float64 in
+                                                tests/profile_ref.py.
 
 Everything is accumulated in fp64 on the device, in fixed orders (bitwise reproducible), and the launches allocate and
 synchronise nothing, so an evaluator call can sit in a captured graph.  There is no CPU fallback: CPU tensors raise.
@@ -464,3 +471,213 @@ class FScoreEvaluator:
         if groups:
             out["groups"] = groups
         return out
+
+
+def _threshold_table(thresholds):
+    """(lo, hi, steps) - a sequence of three whose last entry is a Python / numpy integer - is np.linspace(lo, hi, steps);
+    anything else is taken as the table itself.  Returns a float64 array, checked: 2..256 finite ascending values."""
+    if not isinstance(thresholds, _np.ndarray) and hasattr(thresholds, "__len__") and len(thresholds) == 3 and \
+            isinstance(thresholds[2], (int, _np.integer)) and not isinstance(thresholds[2], bool):
+        lo, hi, steps = float(thresholds[0]), float(thresholds[1]), int(thresholds[2])
+        if not 2 <= steps <= 256:
+            raise ValueError(f"thresholds: 2..256 steps expected, got {steps}")
+        t = _np.linspace(lo, hi, steps)
+    else:
+        t = _np.array(thresholds, dtype=_np.float64).reshape(-1)
+    if not 2 <= t.size <= 256:
+        raise ValueError(f"thresholds: a table of 2..256 values expected, got {t.size}")
+    if not _np.isfinite(t).all() or not (_np.diff(t) > 0).all():
+        raise ValueError("thresholds: finite, strictly ascending values expected")
+    return _np.ascontiguousarray(t)
+
+
+def profile_curves(total, count, hist, t):
+    """The derived figures of error totals (host, float64): total [...], count [...], hist [..., K + 1] ->
+    mean [...] = total / count, pck [..., K] = cumsum(hist)[..., :K] / count (the share of points with e <= t[k]) and
+    auc [...] = sum_k (pck[k] + pck[k + 1]) / 2 * (t[k + 1] - t[k]) / (t[K - 1] - t[0]).  count == 0 gives NaN."""
+    total, count = _np.asarray(total, _np.float64), _np.asarray(count)
+    hist, t = _np.ascontiguousarray(hist), _np.asarray(t, _np.float64)
+    with _np.errstate(invalid="ignore", divide="ignore"):
+        n = count.astype(_np.float64)
+        mean = total / n
+        pck = _np.ascontiguousarray(_np.cumsum(hist, axis=-1)[..., :-1] / n[..., None])
+        auc = _np.sum((pck[..., :-1] + pck[..., 1:]) / 2 * _np.diff(t), axis=-1) / (t[-1] - t[0])
+    return mean, pck, auc
+
+
+class ErrorProfile:
+    """ep = ErrorProfile(n_points, thresholds=(0.0, 50.0, 100), align=False, root=None, per_point=True, gt_scale=1.0,
+                         n_groups=32)
+    out = ep(pred, gt, valid=None, B_real=None, group=None)
+    totals = ep.summary();  ep.reset()
+
+    Where the error sits and how it is distributed: per-point distances between corresponding points (joints or vertices),
+    binned against a threshold table, accumulated per group and per point (p2m_error_profile; include/p2m.h has the
+    definition, tests/profile_ref.py restates it in float64).  Per sample, in fp64: `root` (a point index or None) - both
+    sets minus their own point `root`; `align` - the prediction similarity-aligned onto the ground truth over the valid
+    points (MeshEvaluator's pa_mesh solve); e_i = |p_i - g_i|; bin_i = the first k with e_i <= thresholds[k], K if there is
+    none.  pred, gt: [B, n_points, 3] CUDA tensors, gt read times gt_scale; valid: [B, n_points] (non-zero = counted), any
+    dtype; B_real, group: as MeshEvaluator's.  thresholds: (lo, hi, steps) with an integer `steps` (np.linspace(lo, hi, steps),
+    uploaded bit for bit) or an ascending table of 2..256 values, in the unit of the prediction.
+
+    A call launches on the current stream and returns per-sample device tensors: "error" [B, n_points] fp64 (0 where not
+    counted), "sample_mean" [B] fp64 and "sample_pck" [B, K + 1] int32 (the sample's points per bin; its cumulative sum over
+    the points counted is the sample's PCK curve).  They are buffers reused per batch size, overwritten by the next call of
+    the same size.  The call adds the batch to running totals on the device (fp64 sums in sample order, int64 counts and
+    bins), per group and - with per_point - per point: no allocation after the first call of a size and no sync, so a call
+    can sit in a single-stream captured graph."""
+
+    def __init__(self, n_points, thresholds=(0.0, 50.0, 100), align=False, root=None, per_point=True, gt_scale=1.0,
+                 n_groups=32):
+        self.n_points, self.n_groups = int(n_points), int(n_groups)
+        self.align, self.per_point, self.gt_scale = bool(align), bool(per_point), float(gt_scale)
+        if self.n_points < 1:
+            raise ValueError("n_points < 1")
+        if not 0 <= self.n_groups <= 65535:
+            raise ValueError("n_groups outside 0..65535")
+        self.root = -1 if root is None else int(root)
+        if root is not None and not 0 <= self.root < self.n_points:
+            raise ValueError(f"root: None or a point index in [0, {self.n_points}), got {root}")
+        self.thresholds = _threshold_table(thresholds)
+        self.K = int(self.thresholds.size)
+        self._dev = None
+        self._bufs = {}
+        self.state = None
+
+    def _layout(self):
+        """Offsets (in 8-byte words) of the running totals inside self.state: one buffer, so reset() is one fill and summary()
+        one copy."""
+        G, K, N = self.n_groups + 1, self.K, self.n_points if self.per_point else 0
+        sizes = (("group_sum", G), ("group_count", G), ("group_hist", G * (K + 1)), ("point_sum", N), ("point_count", N),
+                 ("point_hist", N * (K + 1)))
+        off, o = {}, 0
+        for k, n in sizes:
+            off[k] = (o, n)
+            o += n
+        return off, o
+
+    def _device_tables(self, dev):
+        if self._dev is None or self._dev[0] != dev:
+            off, n = self._layout()
+            self.state = torch.zeros(n, device=dev, dtype=torch.int64)
+            views = {k: self.state[o:o + m] for k, (o, m) in off.items() if m}
+            for k in ("group_sum", "point_sum"):
+                if k in views:
+                    views[k] = views[k].view(torch.float64)
+            self._dev = (dev, views, torch.from_numpy(self.thresholds).to(dev))
+            self._bufs = {}
+        return self._dev[1], self._dev[2]
+
+    def reset(self):
+        """Clears the running totals (a device-side fill on the current stream)."""
+        if self.state is not None:
+            self.state.zero_()
+
+    def _buffers(self, B, dev):
+        b = self._bufs.get(B)
+        if b is None:
+            n = int(_lib.hip().p2m_error_profile_workspace(B, self.n_points))
+            b = {"error": torch.zeros((B, self.n_points), device=dev, dtype=torch.float64),
+                 "sample_mean": torch.zeros((B,), device=dev, dtype=torch.float64),
+                 "sample_pck": torch.zeros((B, self.K + 1), device=dev, dtype=torch.int32),
+                 "group": torch.full((B,), -1, device=dev, dtype=torch.int32),
+                 "valid": torch.zeros((B, self.n_points), device=dev, dtype=torch.uint8),
+                 "ws": torch.empty(max(n, 16), device=dev, dtype=torch.uint8), "ws_bytes": n}
+            self._bufs[B] = b
+        return b
+
+    @torch.no_grad()
+    def __call__(self, pred, gt, valid=None, B_real=None, group=None):
+        for x in (pred, gt):
+            if not isinstance(x, torch.Tensor) or x.dim() != 3 or tuple(x.shape[1:]) != (self.n_points, 3) or \
+                    x.shape != pred.shape:
+                raise ValueError(f"pred / gt: expected equal [B, {self.n_points}, 3] tensors, got "
+                                 f"{tuple(getattr(x, 'shape', ()))}")
+        B = int(pred.shape[0])
+        B_real = B if B_real is None else int(B_real)
+        if not 0 <= B_real <= B:
+            raise ValueError(f"B_real = {B_real} outside [0, {B}]")
+        if valid is not None and (not isinstance(valid, torch.Tensor) or tuple(valid.shape) != (B, self.n_points)):
+            raise ValueError(f"valid: expected a [{B}, {self.n_points}] tensor, got {tuple(getattr(valid, 'shape', ()))}")
+        pred, gt = _cuda_f32(pred, "pred"), _cuda_f32(gt, "gt")
+        dev = pred.device
+        if valid is not None and not valid.is_cuda:
+            raise _lib.P2MError("valid: the evaluation kernels need a CUDA tensor (there is no CPU path)")
+        views, th = self._device_tables(dev)
+        buf = self._buffers(B, dev)
+        val = None
+        if valid is not None:
+            val = buf["valid"]
+            torch.ne(valid, 0, out=val.view(torch.bool))
+        grp = None
+        if group is not None:
+            grp = buf["group"]
+            if isinstance(group, torch.Tensor) and group.is_cuda:
+                g = group.reshape(-1)[:B].to(torch.int32)
+            else:
+                g = torch.as_tensor(_np.asarray(group, dtype=_np.int32).reshape(-1)[:B]).to(dev, non_blocking=True)
+            if g.numel() < B_real:
+                raise ValueError(f"group: need >= {B_real} ids, got {g.numel()}")
+            grp[:g.numel()].copy_(g)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.hip().p2m_error_profile(
+                _p(pred), _p(gt), _p(val), B, B_real, self.n_points, self.gt_scale, self.root, int(self.align), _p(th), self.K,
+                _p(buf["ws"]), buf["ws_bytes"], _p(buf["error"]), _p(buf["sample_mean"]), _p(buf["sample_pck"]), _p(grp),
+                self.n_groups, _p(views["group_sum"]), _p(views["group_count"]), _p(views["group_hist"]),
+                _p(views.get("point_sum")), _p(views.get("point_count")), _p(views.get("point_hist")), _stream()),
+                "p2m_error_profile")
+        return {k: buf[k] for k in ("error", "sample_mean", "sample_pck")}
+
+    def totals(self):
+        """Syncs once.  The raw running totals as host arrays: group_sum [n_groups + 1] fp64, group_count [n_groups + 1] and
+        group_hist [n_groups + 1, K + 1] int64 (row 0: overall) and, with per_point, point_sum [n_points] fp64, point_count
+        [n_points] and point_hist [n_points, K + 1] int64; None before the first call."""
+        if self.state is None:
+            return None
+        host = self.state.cpu().numpy()
+        off, _ = self._layout()
+        out = {}
+        for k, (o, n) in off.items():
+            if n:
+                a = host[o:o + n]
+                out[k] = a.view(_np.float64) if k.endswith("_sum") else a
+                if k.endswith("_hist"):
+                    out[k] = out[k].reshape(-1, self.K + 1)
+        return out
+
+    def summary(self):
+        """Syncs once.  Over every sample since the last reset():
+          {"thresholds": t [K], "count": points counted, "mean": their mean error, "pck": [K] the share with e <= t[k],
+           "auc": the area under that curve over t[0] .. t[K - 1] (trapezoids, normalised to 1),
+           "groups": {g: {"count", "mean", "pck", "auc"}} for the groups that counted points,
+           "points": {"count" [N], "mean" [N], "pck" [N, K], "auc" [N]} and "auc_points": the mean of points.auc over the
+           points with count > 0 (FreiHAND's per-keypoint AUC; equal to "auc" when every point is always valid) - with
+           per_point}
+        Nothing counted gives NaN means, curves and areas.  pck_at(summary, x) reads the curve at a threshold of the table."""
+        t = self.thresholds
+        tot = self.totals()
+        if tot is None:
+            return {"thresholds": t, "count": 0}
+        mean, pck, auc = profile_curves(tot["group_sum"], tot["group_count"], tot["group_hist"], t)
+
+        def row(r):
+            return {"count": int(tot["group_count"][r]), "mean": float(mean[r]), "pck": pck[r], "auc": float(auc[r])}
+        out = dict(row(0), thresholds=t)
+        groups = {g: row(g + 1) for g in range(self.n_groups) if tot["group_count"][g + 1] > 0}
+        if groups:
+            out["groups"] = groups
+        if self.per_point:
+            pm, pp, pa = profile_curves(tot["point_sum"], tot["point_count"], tot["point_hist"], t)
+            out["points"] = {"count": tot["point_count"], "mean": pm, "pck": pp, "auc": pa}
+            seen = tot["point_count"] > 0
+            out["auc_points"] = float(_np.mean(pa[seen])) if seen.any() else float("nan")
+        return out
+
+
+def pck_at(summary, threshold):
+    """PCK at one threshold of the table, e.g. pck_at(ep.summary(), 150.0) for PCK@150 mm: the entry of summary["pck"] whose
+    threshold equals `threshold` (KeyError when the table has no such entry - the curve is not interpolated)."""
+    hit = _np.flatnonzero(_np.asarray(summary["thresholds"]) == float(threshold))
+    if hit.size != 1:
+        raise KeyError(f"{threshold} is not a threshold of the table")
+    return float(summary["pck"][int(hit[0])])
