@@ -126,7 +126,8 @@ int p2m_weight_pack(const float* W, float* Wt, float* W2, float* W3, int32_t Fou
  * accumulate!=0 adds into dW/db instead of overwriting.  layout 1: P[chunk][fin][k*Fout+fout] (the
  * gradient taken as X^T [g|Lg|L2g]); layout 2 (K = 1): P[chunk][fout][fin] - a plain Linear's gradient taken as G^T X (the
  * operands of p2m_gemm_tn swapped), already in nn.Linear layout: coalesced on both sides (Pdb is then the wrong column sum:
- * pass NULL and reduce the bias gradient separately).  pdb_stride = row stride of Pdb (the N of the p2m_gemm_tn call).  */
+ * pass NULL and reduce the bias gradient separately).  pdb_stride = row stride of Pdb (the N of the p2m_gemm_tn call); the
+ * first Fout floats of a row count.  db and Pdb may each be NULL: db is then neither written nor read.               */
 int p2m_weight_grad_unpack(const float* P, const float* Pdb, int32_t nchunks, float* dW, float* db,
                            int32_t Fout, int32_t Fin, int32_t K, int32_t accumulate, int32_t layout,
                            int32_t pdb_stride, void* stream);
@@ -325,7 +326,9 @@ int p2m_gemm_tn_rows(p2m_graph_t g, int32_t row_set, int32_t B, const float* A, 
 int p2m_weight_eff(const float* Wt, float* We, int32_t Ka, int32_t N, float a, float b, void* stream);
 /* dW (nn.Linear layout) from the real-vertex partials P[c][fin][k*Fout+fo] plus the fake-vertex partials
  * P2[c][fin][fo] entering plane k with factor (1, s1, s2)[k]; db from both.  accumulate != 0 adds into dW/db (the
- * caller's gradient buffer, e.g. a slice of optim.FlatAdam.flat_grad) instead of overwriting.                      */
+ * caller's gradient buffer, e.g. a slice of optim.FlatAdam.flat_grad) instead of overwriting.  K must be 3.  Pdb rows are
+ * 3 Fout floats wide (the first Fout count), Pdb2 rows Fout.  db, Pdb and Pdb2 may each be NULL: db is written only when db
+ * and Pdb are both given (Pdb2 alone does not reach it); with Pdb2 NULL db is the sum of Pdb alone.                  */
 int p2m_weight_grad_unpack2(const float* P, const float* Pdb, int32_t nchunks, const float* P2, const float* Pdb2,
                             int32_t nchunks2, float s1, float s2, float* dW, float* db, int32_t Fout, int32_t Fin,
                             int32_t K, int32_t accumulate, void* stream);
