@@ -403,7 +403,13 @@ class _MeshNetFn(torch.autograd.Function):
         if g_out.classes:      # class-sum form: a representative carries the gradient of its whole class, holes nothing
             G = ops.class_reduce(g_out, G, B, net.num_mesh_output_chan)
         g_cur = G
-        keep = []          # tensors read by the side stream: kept alive until the join at the end of backward
+        # tensors read by the side stream: kept alive until the join at the end of backward.  EVERY operand that is not owned by
+        # something that outlives the backward belongs here - also the small ones: the (scale, shift) of an activation on
+        # load are views of the previous layer's BatchNorm coefficients, which `saved` drops one layer later, and an amax word
+        # that is only attached to a tensor the side stream does not read dies with that tensor once the chunk has rolled over.
+        # Freed memory goes straight to the main stream's next allocation while a late side stream has not read it yet
+        # (tests/test_gpu_stream_order.py: found with the side stream delayed, pinned by the spy at the join).
+        keep = []
         main_stream = torch.cuda.current_stream()
         side = ops.side_stream(grad_out.device) if ops.DW_SIDE_STREAM else None
 
@@ -566,7 +572,7 @@ class _MeshNetFn(torch.autograd.Function):
                                                                       wc.get((L.ci, "amax"), Wl, lambda: ops.param_amax(Wl))))
                 P0, E1, E2 = ops.conv_pair(gph, B, gy, L.Fout, W2, add, dX, L.Fin, opb, P0=P0)
                 ga = ops.amax_of(gy, gph, B)       # bounds S g (x 2) and the paired planes (x 2^(plane_bits + 1))
-                with side_ctx(keep, X, P0, E1, E2):
+                with side_ctx(keep, X, P0, E1, E2, ga):
                     Pw, Pb, nch = ops.gemm_tn_rows(gph, 3, B, X, L.Fin, 0, [P0, E1, E2], L.Fout, True, g_amax=ga,
                                                    g_bits=gph.plane_bits + 1)
                     Pw2, Pb2, nch2 = ops.gemm_tn_rows(gph, 4, B, X, L.Fin, 0, [P0], L.Fout, False, g_amax=ga, g_bits=1)
@@ -606,7 +612,7 @@ class _MeshNetFn(torch.autograd.Function):
                 # fold_in (forward: ops.fold_act_ok): X is the RAW output of the previous conv, tagged with the bound of its
                 # activated form; both weight-gradient launches apply the activation on load
                 xa_w = ops.amax_of(X) if fold_in is not None else None
-                with side_ctx(keep, X, gy, E1, E2):
+                with side_ctx(keep, X, gy, E1, E2, xa_w, *(fold_in or ())):
                     Pw, Pb, nch = ops.gemm_tn_rows(gph, 1, B, X, L.Fin, x_shift, [gy, E1, E2], L.Fout, True, a_amax=xa_w,
                                                    g_amax=ops.amax_of(gy, gph, B), g_bits=gph.plane_bits, a_act=fold_in)
                     Pw2, Pb2, nch2 = ops.gemm_tn_rows(gph, 2, B, X, L.Fin, x_shift, [gy], L.Fout, False, a_amax=xa_w,

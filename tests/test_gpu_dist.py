@@ -30,12 +30,53 @@ assert world == 2 and torch.distributed.get_backend() == "gloo"
 dev = torch.device("cuda", local)
 gL, _, rev = helpers.golden_graphs("mano")
 c = helpers.loss_case("mano", B=8, seed=23)
-net = pose2mesh_net.get_model(21, gL, mano=True)
-net.load_state_dict(helpers.numpy_state(net.state_dict(), 4))
-net = net.to(dev).train()
-for m in net.modules():
-    if isinstance(m, torch.nn.Dropout):
-        m.p = 0.0
+def build_net():
+    net = pose2mesh_net.get_model(21, gL, mano=True)
+    net.load_state_dict(helpers.numpy_state(net.state_dict(), 4))
+    net = net.to(dev).train()
+    for m in net.modules():
+        if isinstance(m, torch.nn.Dropout):
+            m.p = 0.0
+    return net
+# test-only knobs (tests/stream_skew.py): which rank gets its weight-gradient stream delayed right before each backward(),
+# and which rank its main stream before red.finish(); unset (the default): no skew, nothing below runs
+skew_side = os.environ.get("P2M_TEST_SKEW_SIDE_RANK", "") == str(rank)
+skew_main = os.environ.get("P2M_TEST_SKEW_MAIN_RANK", "") == str(rank)
+late_side = late_main = lambda: None
+if skew_side or skew_main:
+    import time
+    import stream_skew as sk
+    from pose2mesh_release_amd import ops
+    torch.cuda.set_device(dev)
+    sk.reset_budget()
+    sk.calibrate()
+    main_st = torch.cuda.current_stream()
+    side_st = sk.distinct_stream(main_st)
+    ops._side_streams[(local, 0)] = side_st
+    assert sk.bites(main_st, side_st) and sk.bites(side_st, main_st), sk.last_bite
+    # t_step of an unskewed step on a throw-away copy of the model (second pass), then D = max(20 ms, 3 t_step)
+    probe = build_net()
+    px = synth.pose2d_batch(8, 21, seed=31)[:4].to(dev)
+    for _ in range(2):
+        torch.cuda.synchronize()
+        e0, e1, t0 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True), time.perf_counter()
+        e0.record()
+        pm, pl = probe(px)
+        (pm.square().mean() + pl.square().mean()).backward()
+        e1.record()
+        host_ms = (time.perf_counter() - t0) * 1e3
+        torch.cuda.synchronize()
+    t_step = max(host_ms, e0.elapsed_time(e1))
+    D = max(20.0, 3.0 * t_step)
+    assert D <= sk.CAP_CALL_MS, (t_step, D)
+    del probe, pm, pl
+    print(f"SKEW rank {{rank}}: side late {{skew_side}}, main late {{skew_main}}, bites both ways, t_step {{t_step:.3f}} ms, "
+          f"D {{D:.3f}} ms", flush=True)
+    if skew_side:
+        late_side = lambda: sk.delay(side_st, D)
+    if skew_main:
+        late_main = lambda: sk.delay(main_st, D)
+net = build_net()
 opt = optim.FlatAdam(net.parameters(), lr=1e-3)
 # the bench's configuration: MeshNet gradients accumulate in place and are reported to the reducer per layer from inside
 # the backward (autograd's hooks only fire once the whole backward has returned); small buckets so that several of them
@@ -52,7 +93,9 @@ mesh, lift = net(pose2d)
 total, _ = fused(mesh, c["gt_mesh"][sl].to(dev), c["gt_reg3dpose"][sl].to(dev), c["val_mesh"][sl].to(dev),
                  c["val_reg3dpose"][sl].to(dev))
 lift_l = 1e-3 * stock[4](lift, c["gt_lift3dpose"][sl].to(dev), c["val_lift3dpose"][sl].to(dev))
+late_side()
 lift_l.backward()
+late_side()
 total.backward()
 # overlap by construction: a bucket made of MeshNet parameters only was launched while gradients were still arriving
 mesh_ids = {{id(p) for p in net.pose2mesh.parameters()}}
@@ -60,6 +103,7 @@ mesh_only = [b for b, (_, _, idx) in enumerate(red.buckets) if all(id(opt.params
 log, seen_total = list(red.launch_log), red._seen
 early = [seen for b, seen in log if b in mesh_only]
 assert len(mesh_only) >= 2 and early and min(early) <= seen_total - 10, (mesh_only, log, seen_total)
+late_main()
 scale = red.finish()
 assert abs(scale - 0.5) < 1e-12 and len(red.buckets) >= 2
 grads = {{k: (p.grad * scale).cpu().numpy() for k, p in net.named_parameters()}}
@@ -88,13 +132,25 @@ def _launch(nproc, argv, extra_env=None, timeout=900):
     return subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
 
 
-def test_two_ranks_real_model_gradient_is_mean_of_oracle_shard_gradients(hip_libs, tmp_path):
-    import loss_oracle as lo
-    out = str(tmp_path / "dp")
-    script = tmp_path / "worker.py"
+def _run_worker(folder, tag, extra_env=None):
+    """One two-rank gloo run of WORKER; returns (prefix of the files it wrote, its stdout)."""
+    out = str(folder / tag)
+    script = folder / f"worker_{tag}.py"
     script.write_text(WORKER.format(root=ROOT, out=out))
-    r = _launch(2, [str(script)])
+    r = _launch(2, [str(script)], extra_env=extra_env, timeout=300)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    return out, r.stdout
+
+
+@pytest.fixture(scope="module")
+def plain_run(hip_libs, tmp_path_factory):
+    """The unskewed two-rank run, once for the tests that read it."""
+    return _run_worker(tmp_path_factory.mktemp("dp"), "dp")
+
+
+def test_two_ranks_real_model_gradient_is_mean_of_oracle_shard_gradients(hip_libs, plain_run):
+    import loss_oracle as lo
+    out, _ = plain_run
     z = [np.load(out + f"_r{k}.npz") for k in range(2)]
     # both ranks hold the same averaged gradient and, after the step, the same parameters
     for k in z[0].files:
@@ -143,6 +199,29 @@ def test_two_ranks_real_model_gradient_is_mean_of_oracle_shard_gradients(hip_lib
         for k, v in stats[rank].items():
             assert np.abs(z[rank]["s::" + k] - v.numpy()).max() < 1e-4 * max(1.0, float(v.abs().max())), (rank, k)
     assert not np.array_equal(z[0]["s::pose2mesh.bn.0.running_mean"], z[1]["s::pose2mesh.bn.0.running_mean"])
+
+
+def test_two_ranks_skewed_write_the_bytes_of_the_unskewed_run(hip_libs, plain_run, tmp_path):
+    """The same two-rank gloo step with rank 0's weight-gradient stream late before each backward() and rank 1's main
+    stream late before red.finish(): the communication stream must wait for EVERY stream that wrote a bucket, on both
+    ranks.  A two-rank sum is order-free, so the averaged gradients and the updated parameters are the unskewed run's, byte
+    for byte.  The worker installs a side stream that bites against its main stream (tests/stream_skew.py) and sizes the
+    delay from its own measured step."""
+    runs = {}
+    skewed = _run_worker(tmp_path, "skewed", {"P2M_TEST_SKEW_SIDE_RANK": "0", "P2M_TEST_SKEW_MAIN_RANK": "1"})
+    for tag, (out, stdout), lines in (("plain", plain_run, 0), ("skewed", skewed, 2)):
+        skew_lines = [ln for ln in stdout.splitlines() if ln.startswith("SKEW rank")]
+        print("\n".join(skew_lines))
+        assert len(skew_lines) == lines, stdout[-2000:]
+        runs[tag] = ([np.load(out + f"_r{k}.npz") for k in range(2)], [np.load(out + f"_p{k}.npy") for k in range(2)])
+    for k in range(2):
+        za, zb = runs["plain"][0][k], runs["skewed"][0][k]
+        names = [n for n in za.files if n.startswith("g::")]
+        assert len(names) >= 60 and sorted(za.files) == sorted(zb.files)
+        for n in names:
+            assert za[n].tobytes() == zb[n].tobytes(), (k, n)
+        assert runs["plain"][1][k].tobytes() == runs["skewed"][1][k].tobytes(), k
+    assert float(np.abs(runs["plain"][0][0]["g::pose2mesh.cl.5.weight"]).max()) > 0.0
 
 
 def test_bench_two_ranks_on_one_gpu(hip_libs):

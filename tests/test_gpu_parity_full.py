@@ -33,8 +33,10 @@ VERTEX_TOL = 1e-4
 ORACLE_THREADS = 16          # torch's CPU sparse path collapses when a 256-thread host is used fully
 
 
-def _record(key, value):
+def _record(key, value, name=None):
     path = os.path.join(ROOT, "gpurun_out", "parity_maxima.json")
+    if name is not None:         # another test file's figures (test_gpu_stream_order.py): same directory, its own file
+        path = os.path.join(os.path.dirname(path), name)
     os.makedirs(os.path.dirname(path), exist_ok=True)
     try:
         d = json.load(open(path))
