@@ -14,9 +14,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
-HIP_SOURCES = ["capi.hip", "basis.hip", "gemm.hip", "bn.hip", "optim.hip", "loss.hip", "chebtile.hip", "posenet.hip",
-               "eval.hip", "body.hip", "body_bwd.hip", "fscore.hip", "sample.hip", "render.hip", "camfit.hip", "video.hip",
-               "overlay.hip", "annot.hip", "crowd.hip", "shade.hip", "track.hip", "profile.hip"]
+HIP_SOURCES = ["capi.hip", "basis.hip", "gemm_planes.hip", "gemm_tn.hip", "weights.hip", "amax.hip", "bn.hip", "optim.hip",
+               "loss.hip", "chebtile.hip", "posenet.hip", "eval.hip", "body.hip", "body_bwd.hip", "fscore.hip", "sample.hip",
+               "render.hip", "camfit.hip", "video.hip", "overlay.hip", "annot.hip", "crowd.hip", "shade.hip", "track.hip",
+               "profile.hip"]
 # per-source flags.  chebtile.hip: the gather's fmaf chains must stay scalar v_fma_f32 - SLP-packed v_pk_fma_f32 next to the
 # MFMA waves measured 9 % slower over the real-row shapes of a train step (17.2 vs 19.0 ms)
 # fscore.hip: the search loop is 6.5 plain f32 instructions per pair (3 v_sub, v_mul, 2 v_fmac, half a v_min3); SLP-packed it
@@ -37,7 +38,8 @@ HIP_SOURCE_FLAGS = {"chebtile.hip": ["-fno-slp-vectorize"], "fscore.hip": ["-fno
                     "camfit.hip": ["-ffp-contract=off"], "video.hip": ["-ffp-contract=off"],
                     "crowd.hip": ["-ffp-contract=off"], "shade.hip": ["-ffp-contract=off"],
                     "track.hip": ["-ffp-contract=off"], "profile.hip": ["-ffp-contract=off"]}
-HIP_HEADERS = ["p2m_common.h", "p2m_body.h", "p2m_split.h", "p2m_eval.h", "p2m_philox.h", "p2m_render.h", os.path.join("..", "..", "include", "p2m.h")]
+# every header of csrc/ (a source is stale when any of them is newer: none can be forgotten) and the C ABI
+HIP_HEADERS = sorted(n for n in os.listdir(CSRC) if n.endswith(".h")) + [os.path.join("..", "..", "include", "p2m.h")]
 HIP_LIB = os.path.join(LIBDIR, "libp2m_hip.so")
 HOST_LIB = os.path.join(LIBDIR, "libp2m_host.so")
 

@@ -30,7 +30,7 @@ int check_launch(const char* what) {
 }
 
 // P2M_NARROW_ROWS (read once per process): 1 (default) = the kernels whose rows are 12 to 36 bytes wide
-// move their data in whole lines (basis.hip k_expand_small_rows / _tile_rows, bn.hip k_class_reduce3, gemm.hip
+// move their data in whole lines (basis.hip k_expand_small_rows / _tile_rows, bn.hip k_class_reduce3, weights.hip
 // k_conv_weights_images_tiled) or keep a sample's gathers on one L2 (loss.hip k_face_terms / k_vertex_grad in xcd_block_id
 // order); 0 = the forms they replace - the A/B switch, bitwise the same results (tests/test_gpu_narrow_rows.py).
 bool narrow_rows() {

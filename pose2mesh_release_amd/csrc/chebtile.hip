@@ -34,6 +34,7 @@
 // = 158.5 KB (132 KB) -> one block per CU:
 // 4 MFMA waves + 8 producer waves (two per SIMD: the gather is a chain of dependent LDS reads, a second wave fills its
 // latencies) for N <= 128, 4 + 4 for N = 256 (the 128-register accumulator needs the 256-register budget).
+#include "p2m_probe.h"
 #include "p2m_split.h"
 
 #include <cstdlib>

@@ -95,7 +95,7 @@ struct Graph {
 };
 
 // Zero entries appended to every row-set table of the handle (real_ids, fake_ids, pair_real_ids, pair_fake_ids and, with
-// classes, the representatives and their weights).  The deepest reader is the prologue of k_gemm_tn_ws (gemm.hip), which
+// classes, the representatives and their weights).  The deepest reader is the prologue of k_gemm_tn_ws (gemm_tn.hip), which
 // fetches the ids of stages 0 .. 4 of 16 rows without bounds checks, whatever the chunk holds: from the first row of a
 // non-empty chunk (index <= n - 1) it reads 5 stages x 16 rows = 80 entries, i.e. up to index n - 1 + 79 < n + ID_SLACK.
 constexpr int ID_PREFETCH_STAGES = 5, ID_STAGE_ROWS = 16;

@@ -1,6 +1,6 @@
-// Device helpers shared by the contraction kernels (gemm.hip, chebtile.hip): vector types, the two ways an fp32 operand
-// is cut into matrix-core slices (three bf16 slices, exact; two scaled fp16 slices, 22 bits), the XCD-aware block
-// swizzle and the LDS-only block barrier.
+// Device helpers shared by the contraction kernels (gemm_planes.hip, gemm_tn.hip, weights.hip, chebtile.hip): vector types,
+// the two ways an fp32 operand is cut into matrix-core slices (three bf16 slices, exact; two scaled fp16 slices, 22 bits),
+// the XCD-aware block swizzle and the LDS-only block barrier.
 #pragma once
 #include "p2m_common.h"
 

@@ -1,7 +1,7 @@
 """The child process of tests/test_gpu_epilogue_copyout.py: what tests/_child_rows_k1.py's table does not reach.
 
 P2M_EPI_COPYOUT is read once per process by the library, so each arm (0: the 4-byte walk, 1: the staged 16-byte copy-out of
-gemm_epilogue, csrc/gemm.hip) is one run of this file:   python tests/_child_epilogue_copyout.py OUT.npz   under the arm's
+gemm_epilogue, csrc/gemm_planes.hip) is one run of this file:   python tests/_child_epilogue_copyout.py OUT.npz   under the arm's
 environment.  Every launch below runs in bf16x3 and in f16x2 and its C (sentinel rows included), statistics partials and amax
 word are stored bit for bit:
   rows3    row sets with three A planes (k_gemm_planes_ws): the (64, 128, 3) and (32, 32, 3) shapes of
@@ -92,7 +92,7 @@ def _main(out):
         with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
             fn()
         names = sorted({e.name for e in prof.events() if "k_gemm_" in e.name})
-        return np.array(names if names else ["(no kernel of gemm.hip in the profile)"])
+        return np.array(names if names else ["(no kernel of gemm_planes.hip in the profile)"])
 
     for arith in ARITHS:
         for k, (nset, Ka, N) in enumerate(ROWS3):

@@ -178,7 +178,7 @@ def _main(out):
             C, st, amax = run(d, "bf16x3", inp, d["planes"])
         keep("dispatch::" + d["name"], C, st, amax)
         names = sorted({e.name for e in prof.events() if "k_gemm_" in e.name})
-        res["log::" + d["name"]] = np.array(names if names else ["(no kernel of gemm.hip in the profile)"])
+        res["log::" + d["name"]] = np.array(names if names else ["(no kernel of gemm_planes.hip in the profile)"])
     np.savez(out, **res)
 
 

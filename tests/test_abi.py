@@ -38,6 +38,17 @@ def test_code_object_is_gfx950(hip_libs):
     assert b"gfx950" in so and b"k_gemm_planes" in so and b"k_basis_fwd" in so
 
 
+def test_every_hip_source_is_built():
+    """build.HIP_SOURCES is exactly the *.hip files of csrc/: a source that is not listed is never compiled, and every header of
+    csrc/ makes the library stale."""
+    from pose2mesh_release_amd import build
+    on_disk = {n for n in os.listdir(build.CSRC) if n.endswith(".hip")}
+    assert set(build.HIP_SOURCES) == on_disk
+    assert len(build.HIP_SOURCES) == len(on_disk), "a source is listed twice"
+    assert set(build.HIP_SOURCE_FLAGS) <= on_disk
+    assert {n for n in os.listdir(build.CSRC) if n.endswith(".h")} <= set(build.HIP_HEADERS)
+
+
 def test_product_never_imports_oracle():
     """The product path must not route through oracle/ (or any CPU fallback)."""
     pkg = os.path.join(ROOT, "pose2mesh_release_amd")

@@ -1,4 +1,4 @@
-"""-m gpu: the staged 16-byte copy-out of gemm_epilogue (csrc/gemm.hip, P2M_EPI_COPYOUT = 1) against the 4-byte walk (= 0), bit
+"""-m gpu: the staged 16-byte copy-out of gemm_epilogue (csrc/gemm_planes.hip, P2M_EPI_COPYOUT = 1) against the 4-byte walk (= 0), bit
 for bit.  The library reads the knob once per process, so each arm is a child process; the six children are started side by side
 once per module.
   row sets    the unmodified tests/_child_rows_k1.py (nset 1 .. 129, Ka 32 .. 256 and 96, N 32 .. 256, bias / addend / statistics

@@ -1,5 +1,6 @@
-"""-m gpu: the dense contractions of csrc/gemm.hip (k_gemm_planes, k_gemm_planes_ws, k_gemm_tn, k_gemm_tn_ws; flat and row-set
-forms; f32, bf16x3, f16x2) at their row-count and pipeline edges, against the float64 restatements of tests/gemm_ref.py.
+"""-m gpu: the dense contractions of csrc/gemm_planes.hip (k_gemm_planes, k_gemm_planes_ws) and csrc/gemm_tn.hip (k_gemm_tn,
+k_gemm_tn_ws), flat and row-set forms, in f32, bf16x3 and f16x2, at their row-count and pipeline edges, against the float64
+restatements of tests/gemm_ref.py.
 
 The cases are the tables of tests/gemm_ref.py (tests/test_gemm_ref_cpu.py audits what they reach: 1 .. 9 stages of 16 rows and
 every tail of k_gemm_tn_ws, 1 .. 4 stages of 32 rows of k_gemm_tn, 2 .. 12 K chunks of the plane contractions, every tile width,

@@ -1,4 +1,4 @@
-"""-m gpu: the epilogue shared by k_gemm_planes, k_gemm_planes_ws and k_gemm_rows_k1 (csrc/gemm.hip: bias, activation, addend, the
+"""-m gpu: the epilogue shared by k_gemm_planes, k_gemm_planes_ws and k_gemm_rows_k1 (csrc/gemm_planes.hip: bias, activation, addend, the
 stores through the row table, the un-pool pair sums, the BatchNorm partials and the amax word) at small shapes, in all three
 arithmetics, through the C ABI as in tests/test_gpu_gemm_edges.py.
 

@@ -1,5 +1,5 @@
 """-m gpu: the narrow-row kernels behind P2M_NARROW_ROWS (csrc/loss.hip k_face_terms / k_vertex_grad in the block order that keeps
-a sample on one L2, csrc/basis.hip k_expand_small_rows / _tile_rows, csrc/bn.hip k_class_reduce3, csrc/gemm.hip
+a sample on one L2, csrc/basis.hip k_expand_small_rows / _tile_rows, csrc/bn.hip k_class_reduce3, csrc/weights.hip
 k_conv_weights_images_tiled) against the kernels they replace, bit for bit, and against float64 where tests/loss_ref.py and
 tests/basis_ref.py give a reference (at the bars of those files, through the checkers of tests/test_gpu_loss_edges.py).
 

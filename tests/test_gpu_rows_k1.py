@@ -1,4 +1,4 @@
-"""-m gpu: k_gemm_rows_k1 (csrc/gemm.hip), the whole-K kernel of the row-set contractions with one A plane and Ka <= 256 in the
+"""-m gpu: k_gemm_rows_k1 (csrc/gemm_planes.hip), the whole-K kernel of the row-set contractions with one A plane and Ka <= 256 in the
 slice arithmetics, against the kernel it replaces (k_gemm_planes_ws) and against float64.
 
 The library reads P2M_ROWS_K1 once per process, so the two paths are two child processes (tests/_child_rows_k1.py, which also

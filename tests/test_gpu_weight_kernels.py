@@ -1,4 +1,4 @@
-"""-m gpu: the weight kernels of csrc/gemm.hip (k_weight_pack, k_transpose_tiled, k_weight_eff, k_weight_grad_unpack) through
+"""-m gpu: the weight kernels of csrc/weights.hip (k_weight_pack, k_transpose_tiled, k_weight_eff, k_weight_grad_unpack) through
 the C ABI, against the restatements and on the case tables of tests/weight_ref.py (audited by tests/test_weight_ref_cpu.py).
 
 Every output lies between guard words and is prefilled with a NaN bit pattern (overwrite) or with integers (accumulate); the

@@ -1,5 +1,5 @@
 """No GPU: the restatements, bounds and case tables of tests/weight_ref.py, which tests/test_gpu_weight_kernels.py holds the
-weight kernels of csrc/gemm.hip to.
+weight kernels of csrc/weights.hip to.
 
   audit       the tables reach what they are named for: every residue class of the two chunk tails of k_weight_grad_unpack with
               and without a trip of the unrolled loop, both sides of every block edge (256 threads of k_weight_pack /

@@ -27,7 +27,7 @@ import math
 import numpy as np
 
 U = 2.0 ** -24
-UNP_CG = 8                          # chunk groups of k_weight_grad_unpack (csrc/gemm.hip); P is unrolled 4 ways, P2 2 ways
+UNP_CG = 8                          # chunk groups of k_weight_grad_unpack (csrc/weights.hip); P is unrolled 4 ways, P2 2 ways
 UNP_BLOCK = 32                      # output elements per block; the first ceil(Fout / 32) blocks also reduce the bias
 PACK_BLOCK = 256                    # threads per block of k_weight_pack and k_weight_eff
 TILE = 64                           # k_transpose_tiled: 64 x 64 tiles, 16-byte accesses when R and C are multiples of 4
@@ -134,7 +134,7 @@ def prescale_p2(P2, nchunks2, Fout, Fin, s1, s2):
     return np.ascontiguousarray((p * f).reshape(nchunks2, Fin * 3 * Fout))
 
 
-# ---- what a shape reaches (restated from csrc/gemm.hip; the CPU audit reads these) -------------------------------------------
+# ---- what a shape reaches (restated from csrc/weights.hip; the CPU audit reads these) -------------------------------------------
 
 def transpose_arms(R, C, w_off=0, wt_off=0, K=1, w2=False, w3=False):
     """Arms of p2m_weight_pack a call takes.  w_off / wt_off: floats by which W / Wt lie behind a 16-byte boundary."""

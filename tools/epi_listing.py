@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Listing table of the dense contractions (csrc/gemm.hip), as profiles/r08_epilogue_asm_table.txt and r09_copyout_asm_table.txt:
+"""Listing table of the plane contractions (csrc/gemm_planes.hip), as profiles/r08_epilogue_asm_table.txt and
+r09_copyout_asm_table.txt:
 
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S -o gemm.s pose2mesh_release_amd/csrc/gemm.hip
-    python tools/epi_listing.py gemm.s [substring of the kernel names ...]
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S -o gemm_planes.s pose2mesh_release_amd/csrc/gemm_planes.hip
+    python tools/epi_listing.py gemm_planes.s [substring of the kernel names ...]
 
 Per kernel: registers, ScratchSize (bytes per lane), waves per SIMD, LDS bytes | between the first and the last global store of
 the kernel: 4-byte and 16-byte global stores, 4-byte and 16-byte global loads, full waits (s_waitcnt vmcnt(0)), counted waits

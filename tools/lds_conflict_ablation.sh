@@ -11,7 +11,7 @@ VARIANTS="NO_XU NO_P0 NO_CONV LINEAR_X LINEAR_LT LINEAR_A"
 if [ "$1" = build ]; then
   mkdir -p $L/abl
   for v in $VARIANTS; do
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c -fno-slp-vectorize -DP2M_ABL_$v -o $L/abl/chebtile_$v.o $R/pose2mesh_release_amd/csrc/chebtile.hip &
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c -fno-slp-vectorize -DP2M_PROBE_BUILD -DP2M_ABL_$v -o $L/abl/chebtile_$v.o $R/pose2mesh_release_amd/csrc/chebtile.hip &
   done
   wait
   for v in $VARIANTS; do

@@ -7,11 +7,11 @@ L=$R/pose2mesh_release_amd/lib
 V="NOMFMA NOSLICE NOLOAD NOSTORE NOMFMA_NOSLICE NOMFMA_NOSLICE_NOSTORE NOLOAD_NOSTORE"
 if [ "$1" = build ]; then
   mkdir -p $L/abl
-  objs=$(ls $L/obj/*.o | grep -v "/gemm.o")
+  objs=$(ls $L/obj/*.o | grep -v "/gemm_planes.o")
   for v in $V; do
     defs=$(echo $v | sed 's/_/ /g' | sed 's/\([A-Z]*\)/-DP2M_PL_ABL_\1/g')
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c $defs -o $L/abl/gemm_$v.o $R/pose2mesh_release_amd/csrc/gemm.hip 2>/dev/null || exit 1
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $L/abl/libp2m_hip_PL_$v.so $objs $L/abl/gemm_$v.o && rm -f $L/abl/gemm_$v.o
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c -DP2M_PROBE_BUILD $defs -o $L/abl/gemm_planes_$v.o $R/pose2mesh_release_amd/csrc/gemm_planes.hip 2>/dev/null || exit 1
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $L/abl/libp2m_hip_PL_$v.so $objs $L/abl/gemm_planes_$v.o && rm -f $L/abl/gemm_planes_$v.o
   done
   ls $L/abl
 else

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 L=$R/pose2mesh_release_amd/lib
 if [ "$1" = build ]; then
   mkdir -p $L/abl
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c -fno-slp-vectorize -DP2M_TILE_TRACE=${2:-1500} -o $L/abl/chebtile_TRACE.o $R/pose2mesh_release_amd/csrc/chebtile.hip || exit 1
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c -fno-slp-vectorize -DP2M_PROBE_BUILD -DP2M_TILE_TRACE=${2:-1500} -o $L/abl/chebtile_TRACE.o $R/pose2mesh_release_amd/csrc/chebtile.hip || exit 1
   objs=$(ls $L/obj/*.o | grep -v chebtile.o)
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $L/abl/libp2m_hip_TRACE.so $objs $L/abl/chebtile_TRACE.o && rm -f $L/abl/chebtile_TRACE.o
   ls -la $L/abl

@@ -7,11 +7,11 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 L=$R/pose2mesh_release_amd/lib
 if [ "$1" = build ]; then
   mkdir -p $L/abl
-  objs=$(ls $L/obj/*.o | grep -v "/gemm.o")
+  objs=$(ls $L/obj/*.o | grep -v "/gemm_tn.o")
   for v in NOMFMA NOSLICE NOLOAD "NOMFMA -DP2M_TN_ABL_NOSLICE"; do
     tag=$(echo $v | tr -d ' ' | sed 's/-DP2M_TN_ABL_/_/g')
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c -DP2M_TN_ABL_$v -o $L/abl/gemm_$tag.o $R/pose2mesh_release_amd/csrc/gemm.hip 2>/dev/null || exit 1
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $L/abl/libp2m_hip_TN_$tag.so $objs $L/abl/gemm_$tag.o && rm -f $L/abl/gemm_$tag.o
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c -DP2M_PROBE_BUILD -DP2M_TN_ABL_$v -o $L/abl/gemm_tn_$tag.o $R/pose2mesh_release_amd/csrc/gemm_tn.hip 2>/dev/null || exit 1
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $L/abl/libp2m_hip_TN_$tag.so $objs $L/abl/gemm_tn_$tag.o && rm -f $L/abl/gemm_tn_$tag.o
   done
   ls $L/abl
 else
