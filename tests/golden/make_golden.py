@@ -7,7 +7,8 @@ Fixtures (all deterministic: numpy PCG64 weights/inputs, fixed hull meshes):
   graphs_<set>.npz   build_coarse_graphs output of the real lib/graph_utils.py: per-level CSR of L
                      (float64, as the reference returns it), perm[0], perm_reverse
   meshnet_<set>.npz  real lib/models/meshnet.Pose2Mesh: eval + train outputs, updated running stats,
-                     gradient norms (+ a few full gradients) for a seeded upstream gradient
+                     gradient norms (+ a few full gradients) for a seeded upstream gradient, and the record of the
+                     near-kink ReLU elements of that very run ({mode}_kink_layer / _index / _bit, tests/kinks.py)
   flat_<set>.npz     real lib/models/pose2mesh_net.FlatPose2Mesh in eval(): cam_mesh, pose3d
   chebconv.npz       real graph_conv_cheby (cheby_graph_conv.py:5-42) fwd/bwd at several shapes; case 0 here, the
                      others in chebconv.part1.npz (one file would exceed 1 MiB; helpers.golden merges the parts)
@@ -63,6 +64,34 @@ def save_graphs(joint_set):
     return gL, J
 
 
+KINK_WINDOW = 1e-4      # tests/kinks.py: every ReLU input the reference saw this close to 0 is recorded
+
+
+class _ReluRecorder:
+    """Stands in for the reference module's `F` while its forward runs: F.relu is the real one, and every pre-activation
+    within KINK_WINDOW of 0 is noted as (ReLU call order, flat index into the [B, V, F] tensor, y > 0)."""
+
+    def __init__(self):
+        self.layer, self.index, self.bit, self._n = [], [], [], 0
+
+    def __getattr__(self, name):
+        return getattr(torch.nn.functional, name)
+
+    def relu(self, x, *a, **kw):
+        y = x.detach().reshape(-1)
+        idx = torch.nonzero(y.abs() <= KINK_WINDOW).reshape(-1)
+        self.layer.append(torch.full_like(idx, self._n))
+        self.index.append(idx)
+        self.bit.append(y[idx] > 0)
+        self._n += 1
+        return torch.nn.functional.relu(x, *a, **kw)
+
+    def arrays(self, mode):
+        return {f"{mode}_kink_layer": torch.cat(self.layer).numpy().astype(np.int16),
+                f"{mode}_kink_index": torch.cat(self.index).numpy().astype(np.int64),
+                f"{mode}_kink_bit": torch.cat(self.bit).numpy().astype(np.bool_)}
+
+
 def save_meshnet(joint_set, gL, J):
     ns = ref_loader.load("mano" if joint_set == "mano" else "human36")
     B = SETS[joint_set][1]
@@ -76,8 +105,14 @@ def save_meshnet(joint_set, gL, J):
         net.load_state_dict(sd)
         net.train(mode == "train")
         xin = x.clone().requires_grad_(True)
-        with ref_loader.cpu_cuda_shim():
-            y = net(xin)
+        rec, real_F = _ReluRecorder(), ns.meshnet.F
+        ns.meshnet.F = rec              # the masks must come from the run whose gradients are stored (train mode does
+        try:                            # not repeat bit for bit from run to run)
+            with ref_loader.cpu_cuda_shim():
+                y = net(xin)
+        finally:
+            ns.meshnet.F = real_F
+        out.update(rec.arrays(mode))
         g = torch.Generator().manual_seed(gseed)
         w = torch.randn(y.shape, generator=g)
         (y * w).sum().backward()
@@ -265,6 +300,10 @@ if __name__ == "__main__":
         save_loss("human36")
         _, gLh, _, revh, _, _ = ref_graphs("human36")
         save_demo(gLh, revh)
+        sys.exit(0)
+    if sys.argv[1:] == ["meshnet"]:                    # only meshnet_<set>.npz, on the committed graphs
+        for js in ("mano", "human36"):
+            save_meshnet(js, helpers.golden_graphs(js)[0], synth.JOINT_SETS[js][0])
         sys.exit(0)
     if sys.argv[1:] == ["live-mano"]:
         save_live_mano(ref_graphs("mano")[1])

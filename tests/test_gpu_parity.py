@@ -6,11 +6,17 @@ import pytest
 import torch
 
 import helpers
+import kinks
 import meshnet_oracle as mo
 from pose2mesh_release_amd import synth
+from test_gpu_parity_full import ORACLE_THREADS, _record
 
 pytestmark = pytest.mark.gpu
 VERTEX_TOL = 1e-4
+# the reference fixture's own distance from the float64 oracle on the same masks: the bounds that
+# tests/test_oracle.py::test_meshnet_oracle_vs_golden asserts on the CPU (3 x measured, see there)
+REFERENCE_CPU_BOUND = {("eval", "mano"): 3 * 1.34e-6, ("eval", "human36"): 3 * 2.86e-6,
+                       ("train", "mano"): 3 * 2.02e-6, ("train", "human36"): 3 * 3.63e-6}
 
 
 def _net(joint_set, gL, seed=1, flat=False):
@@ -28,24 +34,53 @@ def test_meshnet_vs_reference_golden(hip_libs, joint_set, mode):
     z = helpers.golden(f"meshnet_{joint_set}.npz")
     gL, _, _ = helpers.golden_graphs(joint_set)
     B, J = int(z["B"]), int(z["J"])
-    net = _net(joint_set, gL).train(mode == "train")
+    train = mode == "train"
+    net = _net(joint_set, gL).train(train)
     x = helpers.meshnet_input(B, J, seed=7).cuda().requires_grad_(True)
+    net._tap = []                         # (the hook is live in eval() too: the BatchNorm is then the fixed affine map)
     y = net(x)
     err = helpers.max_vertex_l2(y.detach().cpu(), z[f"{mode}_out"])
     assert err <= VERTEX_TOL, f"max per-vertex L2 {err:.3e}"
-    w = torch.randn(y.shape, generator=torch.Generator().manual_seed(3)).cuda()
-    (y * w).sum().backward()
-    # Gradients are NOT compared in norm here any more (round 1's 2e-2 bound hid real errors and flagged nothing): every
-    # gradient tensor is checked element-wise against the float64 oracle with the ReLU kinks accounted for in
-    # tests/test_gpu_parity_full.py.  What the reference fixture pins exactly: a conv bias in front of a train-mode
-    # BatchNorm has a true gradient of exactly 0, and everything is finite.
+    w = torch.randn(y.shape, generator=torch.Generator().manual_seed(3))
+    (y * w.cuda()).sum().backward()
+    masks_hip = kinks.hip_masks(net._tap)
+    net._tap = None
+    # What the reference fixture pins exactly: a conv bias in front of a train-mode BatchNorm has a true gradient of
+    # exactly 0, and everything is finite.
     P = dict(net.named_parameters())
     assert torch.isfinite(x.grad).all()
+
+    def zero_bias(k):
+        return train and k.startswith("cl.") and k.endswith("bias") and f"bn.{k.split('.')[1]}.weight" in P
     for k in z[f"{mode}_grad_names"]:
         k = str(k)
         assert torch.isfinite(P[k].grad).all(), k
-        if mode == "train" and k.startswith("cl.") and k.endswith("bias") and f"bn.{k.split('.')[1]}.weight" in P:
+        if zero_bias(k):
             assert float(P[k].grad.norm()) < 1e-3 * max(1.0, float(P[k.replace("bias", "weight")].grad.norm()))
+    # The reference's OWN gradients (x.grad, every stored full gradient, the norm of every gradient), with the ReLU kinks
+    # accounted for exactly (tests/kinks.py): A = the kernels' gradients on the kernels' masks, B = the fixture's on the
+    # reference's masks (the float64 oracle's, overridden at the fixture's record of the reference's near-kink elements),
+    # D = G64(kernels' masks) - G64(reference's masks); (A - B) - D is round-off of the kernels (ALIGNED_GRAD_TOL) plus
+    # round-off of the reference (the CPU bound of tests/test_oracle.py::test_meshnet_oracle_vs_golden).
+    torch.set_num_threads(ORACLE_THREADS)
+    sd = helpers.numpy_state(mo.init_state(J, mo.trim_graph_list(gL), bool(z["mano"])), 1)
+    glt, xc = helpers.oracle_graphs(gL), helpers.meshnet_input(B, J, seed=7)
+    own = kinks.oracle_own_masks(sd, glt, xc, bool(z["mano"]), train)
+    masks_ref = kinks.masks_from_record(own, z[f"{mode}_kink_layer"], z[f"{mode}_kink_index"], z[f"{mode}_kink_bit"])
+    acc = kinks.accounted_difference(sd, glt, xc, bool(z["mano"]), w, masks_hip, masks_ref, train)
+    A = {k: p.grad for k, p in P.items()}
+    A["__input__"] = x.grad
+    Bf = {"__input__": z[f"{mode}_gin"]}
+    Bf.update({k[len(mode) + 7:]: z[k] for k in z.files if k.startswith(f"{mode}_grad::")})
+    norms = {str(k): float(n) for k, n in zip(z[f"{mode}_grad_names"], z[f"{mode}_grad_norms"])}
+    assert set(norms) == set(P) and len(Bf) > 20
+    tol = kinks.ALIGNED_GRAD_TOL + REFERENCE_CPU_BOUND[(mode, joint_set)]
+    res = kinks.assert_accounted(A, Bf, acc, tol, skip=zero_bias, norms=norms, what=f"{joint_set} {mode} vs fixture")
+    _record(f"g_meshnet_{joint_set}_{mode}_vs_reference_fixture",
+            {"mask_bits_differing": acc.n_bits, "max_abs_y64_at_a_differing_bit": acc.max_abs_y,
+             "flips_vs_float64_kernels": acc.flips_a, "flips_vs_float64_reference": acc.flips_b,
+             "worst_accounted_residual": res["worst"], "at": res["at"], "tensors": len(res["per"]), "bound": tol})
+    assert max(acc.flips_a, acc.flips_b) <= max(20, 4e-6 * sum(m.numel() for m in own)), (acc.flips_a, acc.flips_b)
     if mode == "train":
         for k, v in net.state_dict().items():
             if "running" in k:
@@ -71,7 +106,11 @@ def test_flat_model_vs_reference_golden(hip_libs, joint_set):
     # the fixture's batch is 2 / 4: since round 6 such batches run on posenet.hip too (zero-padded), not on stock modules
     assert summ.get("pn_gemm", {}).get("launches", 0) == 6, summ.keys()
     assert helpers.max_vertex_l2(mesh.cpu(), z["cam_mesh"]) <= VERTEX_TOL
-    assert np.abs(pose3d.cpu().numpy() - z["pose3d"]).max() < 1e-3 * max(1.0, np.abs(z["pose3d"]).max())
+    # the bound tests/test_gpu_posenet.py asserts for the same kernels against float64 (the fixture is 1.4e-7 from float64)
+    d = float(np.abs(pose3d.cpu().numpy() - z["pose3d"]).max())
+    bound = 5e-5 * max(1.0, float(np.abs(z["pose3d"]).max()))
+    _record(f"g_flat_{joint_set}_pose3d_vs_reference_fixture", {"max_abs_diff": d, "bound": bound})
+    assert d <= bound, d
 
 
 def test_graph_conv_cheby_vs_reference_golden(hip_libs):
@@ -224,11 +263,13 @@ def test_edge_cases(hip_libs):
 
 def test_fake_vertex_split_network_equivalence(hip_libs):
     """The real/fake row-set launches (ops.SPLIT_FAKE) give the same network output and gradients as the unsplit
-    kernels (SMPL-like levels: 41 % padding vertices at the finest level)."""
+    kernels (SMPL-like levels: 41 % padding vertices at the finest level).  Two fp32 evaluations, each within
+    ALIGNED_GRAD_TOL of float64 on its own masks: the ReLU masks of both runs are tapped, what their differing bits do to
+    every gradient is subtracted in float64 (tests/kinks.py), and the rest is held to 2 x ALIGNED_GRAD_TOL."""
     from pose2mesh_release_amd import ops
     gL, _, _ = helpers.golden_graphs("human36")
     x = helpers.meshnet_input(2, 17, seed=5)
-    outs, grads = [], []
+    outs, grads, masks = [], [], []
     old = ops.SPLIT_FAKE
     try:
         for flag in (True, False):
@@ -236,15 +277,24 @@ def test_fake_vertex_split_network_equivalence(hip_libs):
             net = _net("human36", gL, seed=4).train()
             assert any(g.split for g in net._graph_cache.on(torch.device("cuda", 0))) == flag
             xg = x.cuda().requires_grad_(True)
+            net._tap = []
             y = net(xg)
-            w = torch.randn(y.shape, generator=torch.Generator().manual_seed(9)).cuda()
-            (y * w).sum().backward()
+            w = torch.randn(y.shape, generator=torch.Generator().manual_seed(9))
+            (y * w.cuda()).sum().backward()
+            masks.append(kinks.hip_masks(net._tap))
+            net._tap = None
             outs.append(y.detach())
             grads.append({k: p.grad.clone() for k, p in net.named_parameters()})
+            grads[-1]["__input__"] = xg.grad.clone()
     finally:
         ops.SPLIT_FAKE = old
     assert helpers.max_vertex_l2(outs[0].cpu(), outs[1].cpu()) <= 2e-5
-    for k in grads[0]:
-        if k.startswith("cl.") and k.endswith("bias") and k != "cl.20.bias":
-            continue                      # exactly-zero gradients in front of train-mode BatchNorm (round-off only)
-        assert helpers.rel_l2(grads[0][k].cpu(), grads[1][k].cpu()) < 2e-2, k
+    torch.set_num_threads(ORACLE_THREADS)
+    sd = helpers.numpy_state(mo.init_state(17, mo.trim_graph_list(gL), False), 4)
+    acc = kinks.accounted_difference(sd, helpers.oracle_graphs(gL), x, False, w, masks[0], masks[1], True)
+    # exactly-zero gradients in front of train-mode BatchNorm (round-off only) are left out
+    res = kinks.assert_accounted(grads[0], grads[1], acc, 2 * kinks.ALIGNED_GRAD_TOL, what="split vs unsplit",
+                                 skip=lambda k: k.startswith("cl.") and k.endswith("bias") and k != "cl.20.bias")
+    _record("g_fake_vertex_split_vs_unsplit",
+            {"mask_bits_differing": acc.n_bits, "max_abs_y64_at_a_differing_bit": acc.max_abs_y,
+             "worst_accounted_residual": res["worst"], "at": res["at"], "bound": 2 * kinks.ALIGNED_GRAD_TOL})
